@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the sparse-search hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up the headline workload, warm up, time K steps, write the
+outputs of the last timed step if --dump-outputs is given, print the line. --full adds everything else the benchmark
+measures and checks: the roofline (with its own peak-rate and copy measurements), Recall@k, the CPU baseline and parity
+sample, the host-inclusive figures and the extra objects below.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step returned to a caller, as DIR/<name>.npy
+(float32 / float64): doc_ids (external ids, -1 past n_hits), scores (f32 as returned), scores_exact (the exact u32
+scores), n_hits. The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+Above DUMP_MAX_BYTES a fixed, seeded sample of the queries is written, with their rows in query_rows.npy.
 
 N > 1 without a launcher: this process starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
 child BEFORE anything touches the GPU, relays rank 0's JSON line and exits with the child's status (the reference's
@@ -14,7 +24,7 @@ query of the batch, with the index and the CSR queries already resident in HBM.
 Headline workload (BASELINE.json metric, configs[1]): Flickr30K-shape text->image sparse search, top-10.
   N > 1: the reference's own data parallelism (src/search.py:180-182): every rank holds the (16 MB) index and scores
   its own queries; no data-path collective; "scaling": "weak".
-Extra objects (never part of `value`):
+Extra objects (--full only; never part of `value`):
   "c3_coco5k"  configs[2]: COCO-5K shapes, both directions, 1 GPU.
   "c4_1m"      configs[3], the north-star target: 1 M docs / 10 000 queries; at N > 1 the index is doc-range sharded over
                the ranks and the per-shard top-k lists are merged after ONE RCCL all-gather (exact), "scaling": "strong";
@@ -58,6 +68,8 @@ N_XCDS = 8
 COUNTERS_FILE = os.path.join(ROOT, "profiles", "r03_counters.json")
 LDS_PEAK_GBS = 256 * 128 * 2.4  # 128 B / clk / CU x 256 CUs x 2.4 GHz = 78.6 TB/s (guide figure; the measured one is used)
 
+DUMP_MAX_BYTES = 60 * 10**6   # --dump-outputs stays under 64 MB, npy headers included
+
 EXIT_LAUNCH = 2   # bad launch: fewer GPUs than ranks, WORLD_SIZE / --gpus mismatch
 EXIT_HUNG = 3     # the multi-rank exchange did not finish (watchdog)
 EXIT_COMM = 4     # RCCL communicator did not come up / exchange failed
@@ -80,8 +92,13 @@ def phase(name, rank=None):
 def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them (>= 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: roofline, recall, CPU baseline and parity, "
+                         "host-inclusive figures, the c3 / c4 / c5 objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last timed step's results to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--flickr-images", type=int, default=31014)
     ap.add_argument("--tile-docs", type=int, default=0)
     ap.add_argument("--c4-docs", type=int, default=1_000_000)
@@ -112,7 +129,13 @@ def parse_args(argv):
                     help="(rehearsal on a small box) let several ranks share one GPU instead of failing")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="ranks only rendezvous (gloo), barrier, max-reduce and print; no GPU work (CPU test of the launcher)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.only_c3 or args.only_c4 or args.only_c5) and (not args.full or args.dump_outputs):
+        ap.error("--only-c3 / --only-c4 / --only-c5 select objects of --full (add --full) and skip the headline, "
+                 "whose results --dump-outputs writes")
+    return args
 
 
 def visible_gpus():
@@ -578,6 +601,24 @@ def cpu_baseline(wl, got, target_seconds, threads, rows=True):
 
 
 # ------------------------------------------------------------------------------------------------ workloads
+def dump_outputs(out_dir, ix, got, k):
+    """--dump-outputs: the results of one search as a caller receives them (QueryBatch.fetch), with the ordinals resolved
+    to external doc ids, since ordinals depend on the index layout while ids and scores are the answer."""
+    ords, f32, u32, n = got
+    ids = ix.docid_table().astype(np.float64)[np.minimum(ords, ix.n_docs - 1)]
+    arrays = {"doc_ids": np.where(np.arange(k)[None, :] < n[:, None], ids, -1.0), "scores": f32,
+              "scores_exact": u32.astype(np.float64), "n_hits": n.astype(np.float64)}
+    row_bytes = sum(a.nbytes for a in arrays.values()) // len(n)
+    if row_bytes * len(n) > DUMP_MAX_BYTES:   # a fixed, seeded sample of the queries (+ 8 B per row for query_rows)
+        rows = np.sort(np.random.default_rng(0).choice(len(n), DUMP_MAX_BYTES // (row_bytes + 8), replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] wrote {', '.join(arrays)} ({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB) to {out_dir}")
+
+
 def run_headline(args, ranks, m, wlmod):
     seed = 1
     t0 = time.perf_counter()
@@ -614,9 +655,12 @@ def run_headline(args, ranks, m, wlmod):
                          "run here, so the scorer's parity is unpinned (DESIGN.md §3)",
         "runtime": m.runtime_info(),
     }
+    if ranks.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ix, batch.fetch(), wl.k)
     devices = ranks.gather_objects({"rank": ranks.rank, "device": ix.device})
     if ranks.rank == 0:
         out["rank_devices"] = devices
+    if ranks.rank == 0 and args.full:
         out["roofline"] = sparse_roofline(batch, wl.k, score_ms, wl.name)
         out["roofline"]["merge_kernel_ms"] = round(merge_ms, 4)
         got = batch.fetch()
@@ -1072,13 +1116,13 @@ def main():
     status = {"exit": 0}
     if not only:
         out = run_headline(args, ranks, m, wlmod)
-    if ranks.world == 1 and not args.no_c3 and (args.only_c3 or not only):
+    if args.full and ranks.world == 1 and not args.no_c3 and (args.only_c3 or not only):
         try:
             out["c3_coco5k"] = run_c3(args, ranks, m, wlmod)
         except Exception as e:
             out["c3_coco5k"] = {"error": f"{type(e).__name__}: {e}"}
             log(f"[bench] c3_coco5k failed: {out['c3_coco5k']['error']}")
-    if ranks.world == 1 and not args.no_c5 and (args.only_c5 or not only):
+    if args.full and ranks.world == 1 and not args.no_c5 and (args.only_c5 or not only):
         for name, shape in (("c5_hybrid", "t2i"), ("c5_hybrid_i2t", "i2t")):
             if args.c5_shape not in ("both", shape):
                 continue
@@ -1088,7 +1132,7 @@ def main():
                 out[name] = {"error": f"{type(e).__name__}: {e}"}
                 log(f"[bench] {name} failed: {out[name]['error']}")
     hung = False
-    if not args.no_c4 and (args.only_c4 or not only):
+    if args.full and not args.no_c4 and (args.only_c4 or not only):
         # The extra object must never take the headline NUMBER down: exceptions are caught and recorded, and at N > 1 a
         # watchdog bounds the wait so that the JSON line is printed regardless — but a failure or a hang there still
         # ends the run with a non-zero status.

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=$1; shift
-B="python3 bench.py --no-cpu --steps 3 --warmup 1 $@"
+B="python3 bench.py --full --no-cpu --steps 3 --warmup 1 $@"
 rm -rf gpurun_out/pl_${TAG}_a gpurun_out/pl_${TAG}_b
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum WRITE_SIZE --output-format csv -d gpurun_out/pl_${TAG}_a -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pl_${TAG}_b -- $B > /dev/null 2>&1

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=$1; shift
-B="python3 bench.py --no-cpu --steps 3 --warmup 1 $@"
+B="python3 bench.py --full --no-cpu --steps 3 --warmup 1 $@"
 rm -rf gpurun_out/pm_${TAG}
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/pm_${TAG} -- $B > /dev/null 2>&1
 python3 - <<PY

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=$1; shift
-B="python3 bench.py --no-cpu --steps 3 --warmup 1 $@"
+B="python3 bench.py --full --no-cpu --steps 3 --warmup 1 $@"
 rm -rf gpurun_out/pq_${TAG}_a gpurun_out/pq_${TAG}_s
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pq_${TAG}_s -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/pq_${TAG}_a -- $B > /dev/null 2>&1

@@ -1,5 +1,7 @@
-# usage: bash scripts/gpu_pmc_wide.sh <tag> [bench args] -> gpurun_out/pmcw_<tag>.txt : wide counter sweep of score_tiles
+# usage: bash scripts/gpu_pmc_wide.sh <tag> [bench args] -> $OUT_DIR/pmcw_<tag>.txt : wide counter sweep of score_tiles
 cd $GRAFT_REPO_ROOT
+export OUT_DIR=${OUT_DIR:-prof_out}
+mkdir -p $OUT_DIR
 export TMPDIR=/tmp
 TAG=$1; shift
 i=0
@@ -10,14 +12,15 @@ for set in \
  "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_INSTS_SENDMSG SQ_IFETCH" \
  "SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_SMEM SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_CYCLES SQ_WAVES" ; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d gpurun_out/pmcw_${TAG}_$i -- python3 bench.py --no-cpu --steps 2 --warmup 1 "$@" > /dev/null 2> gpurun_out/pmcw_${TAG}_$i.err
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT_DIR/pmcw_${TAG}_$i -- python3 bench.py --full --no-cpu --steps 2 --warmup 1 "$@" > /dev/null 2> $OUT_DIR/pmcw_${TAG}_$i.err
 done
 python3 - "$TAG" <<'PY'
-import csv, glob, collections, sys
+import csv, glob, collections, sys, os
+O = os.environ['OUT_DIR']
 tag = sys.argv[1]
-out = open(f'gpurun_out/pmcw_{tag}.txt', 'w')
+out = open(f'{O}/pmcw_{tag}.txt', 'w')
 for i in range(1, 6):
-    fs = glob.glob(f'gpurun_out/pmcw_{tag}_{i}/*/*counter_collection.csv')
+    fs = glob.glob(f'{O}/pmcw_{tag}_{i}/*/*counter_collection.csv')
     if not fs:
         print(i, 'no data', file=out); continue
     agg = collections.defaultdict(lambda: collections.defaultdict(float)); disp = collections.defaultdict(set)
@@ -29,5 +32,5 @@ for i in range(1, 6):
         n = len(disp[kn])
         for c, v in sorted(agg[kn].items()):
             print(f'{kn} launches={n} {c} {v / n:.4g}', file=out)
-print(open(f'gpurun_out/pmcw_{tag}.txt').read())
+print(open(f'{O}/pmcw_{tag}.txt').read())
 PY

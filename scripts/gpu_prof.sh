@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=$1; WL=$2; shift; shift
 STEPS=5; WARM=1
-B="python3 bench.py --no-cpu --steps $STEPS --warmup $WARM $@"
+B="python3 bench.py --full --no-cpu --steps $STEPS --warmup $WARM $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG}_stats -- $B > gpurun_out/prof_${TAG}.json 2>gpurun_out/prof_${TAG}.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof_${TAG}_fetch -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d gpurun_out/prof_${TAG}_l2 -- $B > /dev/null 2>&1

@@ -20,4 +20,4 @@ for rep in range(3):
 " > $O/${R}_peak_rates.txt 2>&1
 [ -x build/latency_lab ] && build/latency_lab > $O/${R}_latency_lab.txt 2>&1
 mkdir -p profiles && cp $O/${R}_counters.json profiles/${R}_counters.json
-python3 bench.py > $O/${R}_bench.json 2> $O/${R}_bench.err; echo "bench rc=$?" | tee -a $O/${R}_prof.log
+python3 bench.py --full > $O/${R}_bench.json 2> $O/${R}_bench.err; echo "bench rc=$?" | tee -a $O/${R}_prof.log

@@ -227,6 +227,19 @@ typedef struct msr_dense msr_dense;
 int msr_dense_open(const uint16_t* p_fp16, uint64_t n, uint32_t h, int device, msr_dense** out);
 int msr_dense_search(msr_dense* dx, const uint16_t* q_fp16, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
                      int32_t* out_n, float* gemm_ms, float* select_ms);
+/* ---- f32 flat search: tevatron's FaissFlatSearcher as the reference runs it without --use_gpu (a plain f32 faiss
+ * IndexFlatIP on the CPU: src/arguments.py:63, src/search.py:232-237; the dense-only recipe scripts/search_dense.sh).
+ * p / q are row-major f32 matrices ([n][h] / [nq][h], any h >= 1, inputs expected finite). Numeric contract: every
+ * score is the k-ordered fmaf chain
+ *     s = fmaf(q[h-1], p[h-1], ... fmaf(q[1], p[1], fmaf(q[0], p[0], +0.0f)))
+ * bit for bit (v_mfma_f32_32x32x2_f32, one accumulator per score, no split-K, subnormals kept), so a score does not
+ * depend on the batch it was searched in. Outputs, key map, padding and tie rule (lower ROW wins) are those of
+ * msr_dense_search; 1 <= k <= MSR_KMAX. A handle holds one precision: msr_dense_search on an f32 handle,
+ * msr_dense_search_f32 on an fp16 handle and msr_hybrid_search with an f32 handle fail with MSR_E_INVAL.
+ * msr_dense_close and msr_dense_stats serve both kinds. */
+int msr_dense_open_f32(const float* p, uint64_t n, uint32_t h, int device, msr_dense** out);
+int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
+                         int32_t* out_n, float* gemm_ms, float* select_ms);
 void msr_dense_close(msr_dense* dx);
 /* Bookkeeping of a dense handle: out = {hipMalloc calls made for its scratch so far, scratch bytes it holds, rows, dim}.
  * The scratch of msr_dense_search / msr_hybrid_search stays with the handle and is only ever grown, so repeated calls of

@@ -88,6 +88,8 @@ SYMBOLS = [
     ("msr_merge_lists", _I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_dense_open", _I, [_VP, _U64, _U32, _I, C.POINTER(_VP)]),
     ("msr_dense_search", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("msr_dense_open_f32", _I, [_VP, _U64, _U32, _I, C.POINTER(_VP)]),
+    ("msr_dense_search_f32", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("msr_dense_close", None, [_VP]),
     ("msr_dense_stats", _I, [_VP, _VP]),
     ("msr_f32_to_f16", _I, [_VP, _VP, _U64, _I]),

@@ -4,6 +4,8 @@
     python -m mllm_sparse_retrieval_amd index  --input out/ [--index out/index] --threads 16       (sparse_index.sh)
     python -m mllm_sparse_retrieval_amd search --sparse_index out/ --depth 10 --query_type text \\
            --dataset_name flickr --queries out/query.tsv --qrels out/qrels.csv --save_dir runs/   (search_sparse.sh)
+    python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
+           --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
 
     python -m mllm_sparse_retrieval_amd eval   --runs_dir runs/ --qrels out/qrels.csv --dataset_name flickr \
            --query_type text [--compat-denominator --world_size 4]                                (recall of TREC runs)
@@ -104,7 +106,26 @@ def read_queries(path):
     return ids, texts
 
 
+def normalize_rows(q):
+    """F.normalize(q, dim=-1) as the reference applies it to the query reps (src/search.py:342), in f32."""
+    import numpy as np
+
+    q = np.asarray(q, dtype=np.float32)
+    return q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), 1e-12)
+
+
+def _check_search_args(a):
+    """Argument checks of `search` that need no index and no GPU."""
+    from ._cabi import MSR_KMAX
+
+    if a.sparse_index is None and a.passage_reps is None:
+        sys.exit("search: give --sparse_index (sparse or hybrid search) and/or --passage_reps (dense search)")
+    if a.sparse_index is None and not 1 <= a.depth <= MSR_KMAX:
+        sys.exit(f"search: dense-only --depth must be in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth})")
+
+
 def _cmd_search(a):
+    _check_search_args(a)
     from .fusion import write_trec_run
     from .qrels import CrossModalQrels
     from .recall import RecallMetrics
@@ -125,6 +146,7 @@ def _cmd_search(a):
         p_reps, p_lookup = pickle_load(files[0])     # files written by this package's own encode step
         q_reps, q_lookup = pickle_load(os.path.join(a.passage_reps, "query.pkl"))
         q_reps_by_id = {str(i): r for i, r in zip(q_lookup, q_reps)}
+    dense_only = a.sparse_index is None
     # one process per GPU under a launcher (src/search.py:115-129); gloo carries the recall fractions only
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1:
@@ -138,10 +160,21 @@ def _cmd_search(a):
             import torch
 
             a.device %= max(torch.cuda.device_count(), 1)
-    searcher = LuceneImpactSearcher(os.path.join(a.sparse_index, "index") if os.path.isdir(
-        os.path.join(a.sparse_index, "index")) else a.sparse_index, None, device=a.device)
-    searcher.set_analyzer(JWhiteSpaceAnalyzer())
-    qids, texts = read_queries(a.queries or os.path.join(a.sparse_index, "query.tsv"))
+    if dense_only:  # scripts/search_dense.sh: the ids of query.pkl in file order, or those --queries lists, in its order
+        searcher = None
+        qids = [str(x) for x in q_lookup]
+        if a.queries:
+            wanted = read_queries(a.queries)[0]
+            missing = [x for x in wanted if x not in q_reps_by_id]
+            if missing:
+                sys.exit(f"search: {len(missing)} ids of {a.queries} have no vector in query.pkl (first: {missing[0]})")
+            qids = wanted
+        texts = [""] * len(qids)
+    else:
+        searcher = LuceneImpactSearcher(os.path.join(a.sparse_index, "index") if os.path.isdir(
+            os.path.join(a.sparse_index, "index")) else a.sparse_index, None, device=a.device)
+        searcher.set_analyzer(JWhiteSpaceAnalyzer())
+        qids, texts = read_queries(a.queries or os.path.join(a.sparse_index, "query.tsv"))
     n_queries = len(qids)
     if world > 1:  # the reference's DistributedSampler split, padding included (src/search.py:180-182)
         from .sampler import distributed_sampler_indices
@@ -155,7 +188,9 @@ def _cmd_search(a):
     sparse_run, dense_run, fusion_run = {}, {}, {}
     args.batch_size, args.quiet = a.batch_size, True
     t0 = time.time()
-    if p_reps is not None and not a.host_fusion:
+    if dense_only:
+        dense_run = _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids)
+    elif p_reps is not None and not a.host_fusion:
         # Hybrid on the GPU (the default): this rank's WHOLE query shard in one msr_hybrid_search call — sparse scores,
         # both depth lists, the reference's fusion (src/hybrid.py:32-53) and the top --fusion_k never leave HBM.
         sparse_run, dense_run, fusion_run = _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts)
@@ -183,9 +218,11 @@ def _cmd_search(a):
     if a.save_dir:
         os.makedirs(a.save_dir, exist_ok=True)
         sfx = f".rank{rank}" if world > 1 else ""
-        write_trec_run(sparse_run, os.path.join(a.save_dir, "sparse.trec" + sfx), name="sparse")
-        if dense_run:
+        if not dense_only:  # (dense-only search writes the dense run alone: no sparse.trec, no fusion.trec)
+            write_trec_run(sparse_run, os.path.join(a.save_dir, "sparse.trec" + sfx), name="sparse")
+        if dense_run or dense_only:
             write_trec_run(dense_run, os.path.join(a.save_dir, "dense.trec" + sfx), name="dense")
+        if dense_run and not dense_only:
             write_trec_run(fusion_run, os.path.join(a.save_dir, "fusion.trec" + sfx))
         if world > 1:  # rank 0 joins the per-rank files (one node, shared directory)
             dist.barrier()
@@ -217,9 +254,30 @@ def _cmd_search(a):
         m.sort_and_count()
         m.all_gather_object()
         m.print_recall()
-    searcher.close()
+    if searcher is not None:
+        searcher.close()
     if world > 1:
         dist.barrier()
+
+
+def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids):
+    """search --passage_reps without --sparse_index (scripts/search_dense.sh): this rank's WHOLE query shard in one
+    DenseIndex.search call. Precision follows the reference (src/search.py:254-270): the f32 flat index it searches on
+    the CPU by default, fp16 storage with --use_gpu. Returns the dense run in the layout of get_run_dict
+    (src/search.py:66-82), --remove_query applied there as the reference does."""
+    import numpy as np
+
+    from .dense import DenseIndex
+    from .run import get_run_dict
+
+    q = normalize_rows(np.stack([q_reps_by_id[x] for x in qids])) if qids else np.zeros((0, p_reps.shape[1]), np.float32)
+    dix = DenseIndex(p_reps, device=a.device, precision="fp16" if a.use_gpu else "f32")
+    try:
+        d_scores, d_idx = dix.search(q, min(a.depth, dix.n))
+    finally:
+        dix.close()
+    lookup = np.asarray([str(x) for x in p_lookup], dtype=object)
+    return get_run_dict(qids, d_scores, lookup[d_idx], a.remove_query)
 
 
 def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
@@ -327,8 +385,11 @@ def main(argv=None):
     i.set_defaults(fn=_cmd_index)
 
     s = sub.add_parser("search")
-    s.add_argument("--sparse_index", required=True)
-    s.add_argument("--passage_reps", default=None)
+    s.add_argument("--sparse_index", default=None,
+                   help="sparse index directory (sparse search; hybrid with --passage_reps)")
+    s.add_argument("--passage_reps", default=None,
+                   help="dense reps directory (corpus*.pkl + query.pkl); without --sparse_index: dense-only search "
+                        "(scripts/search_dense.sh), f32 unless --use_gpu")
     s.add_argument("--depth", type=int, default=1000)
     s.add_argument("--threads", type=int, default=1)
     s.add_argument("--batch_size", type=int, default=128)
@@ -338,7 +399,9 @@ def main(argv=None):
     s.add_argument("--dataset_name", default="flickr")
     s.add_argument("--save_dir", default=None)
     s.add_argument("--quiet", action="store_true")
-    s.add_argument("--use_gpu", action="store_true")
+    s.add_argument("--use_gpu", action="store_true",
+                   help="dense-only search: fp16 passage storage like the reference's faiss GPU clone (default f32, "
+                        "its CPU index); ignored by the sparse and hybrid routes")
     s.add_argument("--queries", default=None)
     s.add_argument("--qrels", default=None)
     s.add_argument("--device", type=int, default=0)

@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "msr_accumulate.hpp"
+#include "msr_gemm_f32.hpp"
 #include "msr_gemm_w4.hpp"
 
 using namespace msr;
@@ -370,7 +371,11 @@ __global__ __launch_bounds__(512, 1) void dense_scores_256p(const _Float16* __re
 struct msr_dense {
     int device = -1;
     hipStream_t stream = nullptr;
-    _Float16* d_P = nullptr;  // [n_pad][h]
+    _Float16* d_P = nullptr;  // [n_pad][h]; fp16 handles
+    // f32 handles (msr_dense_open_f32): rows [n_pad][hp] in f32, K zero padded to hp (a multiple of kF32KStep)
+    bool f32 = false;
+    float* d_P32 = nullptr;
+    uint32_t hp = 0;
     uint64_t n = 0;
     uint64_t n_pad = 0;       // multiple of 128 and of tile_docs
     uint32_t h = 0;
@@ -446,11 +451,55 @@ int msr_dense_open(const uint16_t* p_fp16, uint64_t n, uint32_t h, int device, m
     return MSR_OK;
 }
 
+int msr_dense_open_f32(const float* p, uint64_t n, uint32_t h, int device, msr_dense** out) {
+    if (!out) {
+        set_error("msr_dense_open_f32: null output");
+        return MSR_E_INVAL;
+    }
+    *out = nullptr;
+    if ((!p && n) || h == 0 || h > (1u << 20) || n >= (1ull << 31)) {
+        set_error("msr_dense_open_f32: need f32 rows with 1 <= h <= 2^20 and n < 2^31 (got n=%llu, h=%u)",
+                  (unsigned long long)n, h);
+        return MSR_E_INVAL;
+    }
+    int n_dev = 0;
+    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
+        set_error("no usable HIP device %d; there is no CPU dense search path", device);
+        return MSR_E_NODEVICE;
+    }
+    msr_dense* dx = new (std::nothrow) msr_dense;
+    if (!dx) {
+        set_error("out of host memory");
+        return MSR_E_NOMEM;
+    }
+    dx->device = device;
+    dx->n = n;
+    dx->h = h;
+    dx->f32 = true;
+    dx->hp = (h + kF32KStep - 1) / kF32KStep * kF32KStep;  // zero columns: exactly neutral in the fmaf chain
+    dx->tile_docs = n <= 4096 ? 4096 : 8192;
+    dx->n_tiles = (uint32_t)std::max<uint64_t>((n + dx->tile_docs - 1) / dx->tile_docs, 1);
+    dx->n_pad = (uint64_t)dx->n_tiles * dx->tile_docs;
+    const size_t bytes = (size_t)dx->n_pad * dx->hp * 4;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&dx->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc(&dx->d_P32, bytes) != hipSuccess || hipMemset(dx->d_P32, 0, bytes) != hipSuccess ||
+        (n && hipMemcpy2D(dx->d_P32, (size_t)dx->hp * 4, p, (size_t)h * 4, (size_t)h * 4, n, hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("device setup of the f32 dense index failed (%zu bytes)", bytes);
+        if (dx->d_P32) (void)hipFree(dx->d_P32);
+        if (dx->stream) (void)hipStreamDestroy(dx->stream);
+        delete dx;
+        return MSR_E_HIP;
+    }
+    *out = dx;
+    return MSR_OK;
+}
+
 void msr_dense_close(msr_dense* dx) {
     if (!dx) return;
     (void)hipSetDevice(dx->device);
     if (dx->d_P_ord) (void)hipFree(dx->d_P_ord);
     if (dx->d_P) (void)hipFree(dx->d_P);
+    if (dx->d_P32) (void)hipFree(dx->d_P32);
     for (void* p : dx->scratch)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : dx->ev)
@@ -519,10 +568,25 @@ static int launch_dense_gemm(msr_dense* dx, const _Float16* P, const _Float16* d
     return MSR_OK;
 }
 
+// The f32 GEMM of an f32 handle: keys of C = Q * P^T into out[q][ld] for doc columns [0, n_cover); Q rows padded to qn_pad
+// (a multiple of 128) and K to dx->hp in the device copy. Doc blocks in slices of at most 65535 (grid y limit).
+static int launch_dense_gemm_f32(msr_dense* dx, const float* d_Q, uint32_t* d_S, uint32_t qn, uint32_t qn_pad,
+                                 uint64_t n_cover, uint64_t ld, hipStream_t st) {
+    for (uint64_t d0 = 0; d0 < n_cover; d0 += 128ull * kMaxGridY) {
+        const uint64_t nd = std::min<uint64_t>(n_cover - d0, 128ull * kMaxGridY);
+        const uint32_t n_left = dx->n > d0 ? (uint32_t)std::min<uint64_t>(dx->n - d0, 0xFFFFFFFFull) : 0u;
+        hipLaunchKernelGGL(dense_scores_f32, dim3(qn_pad / 128, (uint32_t)(nd / 128)), dim3(256), 0, st, d_Q,
+                           dx->d_P32 + d0 * dx->hp, d_S + d0, qn, n_left, dx->hp, ld);
+        HIP_TRY(hipGetLastError());
+    }
+    return MSR_OK;
+}
+
 // to_device = true: out_* are DEVICE buffers ([nq][k] / [nq]) filled on dx->stream (hybrid path); else host buffers.
-static int dense_search_impl(msr_dense* dx, const uint16_t* q_fp16, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
+// q: [nq][h] fp16 (uint16_t) or, on an f32 handle, f32 rows.
+static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
                              int32_t* out_n, float* gemm_ms, float* select_ms, bool to_device, bool unsorted = false) {
-    if (!dx || nq < 0 || (nq && !q_fp16) || !out_idx || !out_key || !out_n) {
+    if (!dx || nq < 0 || (nq && !q_host) || !out_idx || !out_key || !out_n) {
         set_error("msr_dense_search: bad argument");
         return MSR_E_INVAL;
     }
@@ -539,9 +603,10 @@ static int dense_search_impl(msr_dense* dx, const uint16_t* q_fp16, int nq, int 
     const uint32_t qt = (uint32_t)std::min<uint32_t>(qt_pad, std::max(nq, 1));
     int rc = MSR_OK;
     const size_t perq = std::max<size_t>((size_t)qt * k, 1);
+    const size_t q_row = dx->f32 ? (size_t)dx->hp * 4 : (size_t)dx->h * 2;  // bytes per row of the device query copy
     // device scratch and events live on the handle (only ever grown): at the reference's --batch_size 2
     // (scripts/search.sh:29) seven hipMalloc / hipFree pairs per call cost more than the search
-    _Float16* d_Q = (_Float16*)dx->take(msr_dense::S_Q, (size_t)qt_pad * dx->h * 2);
+    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)qt_pad * q_row);
     uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)qt_pad * dx->n_pad * 4);
     uint64_t* d_part = (uint64_t*)dx->take(msr_dense::S_PART, (size_t)dx->n_tiles * perq * 8);
     uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perq * 4);
@@ -560,9 +625,14 @@ static int dense_search_impl(msr_dense* dx, const uint16_t* q_fp16, int nq, int 
     for (int q0 = 0; q0 < nq && rc == MSR_OK; q0 += (int)qt) {
         const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
         const uint32_t qn_pad = (qn + 255) / 256 * 256;
-        bool c = hipMemsetAsync(d_Q, 0, (size_t)qn_pad * dx->h * 2, dx->stream) == hipSuccess &&
-                 hipMemcpyAsync(d_Q, q_fp16 + (size_t)q0 * dx->h, (size_t)qn * dx->h * 2, hipMemcpyHostToDevice,
-                                dx->stream) == hipSuccess &&
+        // f32 rows land in a K-padded copy (zero columns are neutral in the fmaf chain), fp16 rows as they are
+        const size_t h_row = (size_t)dx->h * (dx->f32 ? 4 : 2);
+        bool c = hipMemsetAsync(d_Q, 0, (size_t)qn_pad * q_row, dx->stream) == hipSuccess &&
+                 (q_row == h_row
+                      ? hipMemcpyAsync(d_Q, (const uint8_t*)q_host + (size_t)q0 * h_row, (size_t)qn * h_row,
+                                       hipMemcpyHostToDevice, dx->stream)
+                      : hipMemcpy2DAsync(d_Q, q_row, (const uint8_t*)q_host + (size_t)q0 * h_row, h_row, h_row, qn,
+                                         hipMemcpyHostToDevice, dx->stream)) == hipSuccess &&
                  hipEventRecord(e0, dx->stream) == hipSuccess;
         if (!c) {
             set_error("query upload failed in msr_dense_search");
@@ -573,7 +643,8 @@ static int dense_search_impl(msr_dense* dx, const uint16_t* q_fp16, int nq, int 
         // the select instance: 1024 docs at 4096-doc tiles, 2048 at 8192); padding beyond that is never read
         const uint64_t round_docs = dx->tile_docs == 4096 ? 1024 : 2048;
         const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (dx->n + round_docs - 1) / round_docs * round_docs);
-        rc = launch_dense_gemm(dx, dx->d_P, d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream);
+        rc = dx->f32 ? launch_dense_gemm_f32(dx, (const float*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream)
+                     : launch_dense_gemm(dx, dx->d_P, (const _Float16*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream);
         if (rc != MSR_OK) break;
         (void)hipEventRecord(e1, dx->stream);
         SelectArgs se;
@@ -642,7 +713,20 @@ int msr_dense_stats(const msr_dense* dx, uint64_t out[4]) {
 
 int msr_dense_search(msr_dense* dx, const uint16_t* q_fp16, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
                      int32_t* out_n, float* gemm_ms, float* select_ms) {
+    if (dx && dx->f32) {
+        set_error("msr_dense_search: this handle holds f32 rows (msr_dense_open_f32); search it with msr_dense_search_f32");
+        return MSR_E_INVAL;
+    }
     return dense_search_impl(dx, q_fp16, nq, k, out_idx, out_key, out_n, gemm_ms, select_ms, false);
+}
+
+int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
+                         int32_t* out_n, float* gemm_ms, float* select_ms) {
+    if (dx && !dx->f32) {
+        set_error("msr_dense_search_f32: this handle holds fp16 rows (msr_dense_open); search it with msr_dense_search");
+        return MSR_E_INVAL;
+    }
+    return dense_search_impl(dx, q, nq, k, out_idx, out_key, out_n, gemm_ms, select_ms, false);
 }
 
 }  // extern "C"
@@ -2147,6 +2231,11 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
                       float ms[4]) {
     if (!ix || !dx || !row2ord || !out_ord || !out_score || !out_n || nq < 0) {
         set_error("msr_hybrid_search: bad argument");
+        return MSR_E_INVAL;
+    }
+    if (dx->f32) {
+        set_error("msr_hybrid_search: the dense handle holds f32 rows (msr_dense_open_f32); the hybrid path takes an fp16 "
+                  "handle (msr_dense_open)");
         return MSR_E_INVAL;
     }
     if (!ix->dev) {

@@ -4,8 +4,10 @@ Drop-in for tevatron's FaissFlatSearcher as src/search.py uses it:
     dense_retriever = FaissFlatSearcher(p_reps_0); dense_retriever.add(p_reps_0)        src/search.py:232-237
     all_scores, all_indices = retriever.batch_search(q_reps, depth, batch_size, quiet)  src/search.py:57
     (or retriever.search(q_reps, depth), src/search.py:59)
-The reference keeps the vectors in fp16 on the GPU (co.useFloat16, src/search.py:257,267); so does this class, with
-f32 accumulation on MFMA (msr_dense_search). Ties in score are broken by the lower row index.
+The reference's hybrid run keeps the vectors in fp16 on the GPU (co.useFloat16, src/search.py:257,267); so does this
+class by default, with f32 accumulation on MFMA (msr_dense_search). Its other runs (no --use_gpu, src/arguments.py:63)
+search a plain f32 IndexFlatIP on the CPU: precision="f32" is that search (msr_dense_search_f32), every score the
+k-ordered fmaf chain of f32 inputs. Ties in score are broken by the lower row index.
 """
 from __future__ import annotations
 
@@ -53,32 +55,64 @@ def _as_fp16_rows(x, dim=None, holder=None):
     return np.ascontiguousarray(x16)
 
 
+PRECISIONS = ("fp16", "f32")
+
+
+def _as_f32_rows(x, dim=None):
+    """[rows, dim] matrix -> C-contiguous float32 (float64 rounds to nearest; float32 goes up as it is)."""
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError("expected a [rows, dim] matrix")
+    if dim is not None and x.shape[1] != dim:
+        raise ValueError(f"dimension mismatch: {x.shape[1]} vs {dim}")
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
 class DenseIndex:
-    """fp16 passage matrix resident in HBM.
+    """Passage matrix resident in HBM: fp16 rows (precision="fp16", the default) or f32 rows (precision="f32").
 
     NOT thread-safe per handle (like every libmsr handle: one in-flight call per handle): the fp16 copy of the query
     matrix, the device scratch and the HIP stream all live on the handle and are reused by the next call. Threads that
     search concurrently each open their own DenseIndex."""
 
-    def __init__(self, p_reps, device=0):
-        p16 = _as_fp16_rows(p_reps)
-        self.dim = np.asarray(p_reps).shape[1]
-        self.n = p16.shape[0]
+    def __init__(self, p_reps, device=0, precision="fp16"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
         self._h = C.c_void_p()
-        check(lib().msr_dense_open(ptr(p16.view(np.uint16)), self.n, p16.shape[1], int(device), C.byref(self._h)))
+        if precision == "f32":
+            p32 = _as_f32_rows(p_reps)
+            self.dim = p32.shape[1]
+            self.n = p32.shape[0]
+            check(lib().msr_dense_open_f32(ptr(p32), self.n, self.dim, int(device), C.byref(self._h)))
+        else:
+            p16 = _as_fp16_rows(p_reps)
+            self.dim = np.asarray(p_reps).shape[1]
+            self.n = p16.shape[0]
+            check(lib().msr_dense_open(ptr(p16.view(np.uint16)), self.n, p16.shape[1], int(device), C.byref(self._h)))
         self.last_ms = (0.0, 0.0)
 
-    def search(self, q_reps, k):
-        """-> (scores float32 [nq,k], indices int64 [nq,k]); rows past the hit count hold (-inf, -1) like faiss."""
-        q16 = _as_fp16_rows(q_reps, self.dim, self)   # (consumed by the synchronous call below)
-        nq = q16.shape[0]
+    def search_keys(self, q_reps, k):
+        """-> (row indices uint32 [nq,k], order-preserving u32 score keys [nq,k], hit counts int32 [nq]) as the C-ABI
+        returns them (include/msr.h: 0xFFFFFFFF / key 0 past the hit count)."""
+        if self.precision == "f32":
+            q = _as_f32_rows(q_reps, self.dim)
+            fn, q_ptr = lib().msr_dense_search_f32, ptr(q)
+        else:
+            q = _as_fp16_rows(q_reps, self.dim, self)   # (consumed by the synchronous call below)
+            fn, q_ptr = lib().msr_dense_search, ptr(q.view(np.uint16))
+        nq = q.shape[0]
         idx = np.empty((nq, k), dtype=np.uint32)
         key = np.empty((nq, k), dtype=np.uint32)
         n = np.zeros(nq, dtype=np.int32)
         a, b = C.c_float(), C.c_float()
-        check(lib().msr_dense_search(self._h, ptr(q16.view(np.uint16)), nq, int(k), ptr(idx), ptr(key), ptr(n),
-                                     C.byref(a), C.byref(b)))
+        check(fn(self._h, q_ptr, nq, int(k), ptr(idx), ptr(key), ptr(n), C.byref(a), C.byref(b)))
         self.last_ms = (a.value, b.value)
+        return idx, key, n
+
+    def search(self, q_reps, k):
+        """-> (scores float32 [nq,k], indices int64 [nq,k]); rows past the hit count hold (-inf, -1) like faiss."""
+        idx, key, n = self.search_keys(q_reps, k)
         valid = np.arange(k)[None, :] < n[:, None]
         scores = np.where(valid, keys_to_f32(key), -np.inf).astype(np.float32)
         indices = np.where(valid, idx.astype(np.int64), -1)
@@ -103,13 +137,20 @@ class DenseIndex:
 
 
 class FaissFlatSearcher:
-    """Same call shape as tevatron.retriever.searcher.FaissFlatSearcher (src/search.py:10,232-237,57-59)."""
+    """Same call shape as tevatron.retriever.searcher.FaissFlatSearcher (src/search.py:10,232-237,57-59).
 
-    def __init__(self, init_reps, device=0):
+    tevatron's own class is an f32 faiss IndexFlatIP; the reference searches that on the CPU unless --use_gpu clones
+    it to the GPU with useFloat16 (src/search.py:254-270). precision="f32" matches the CPU run (the k-ordered fmaf chain
+    of f32 inputs, include/msr.h); the default "fp16" matches the --use_gpu run the hybrid script uses."""
+
+    def __init__(self, init_reps, device=0, precision="fp16"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         self._dim = np.asarray(init_reps).shape[1]
         self._parts = []
         self._index = None
         self._device = device
+        self.precision = precision
 
     def add(self, p_reps):
         p = np.asarray(p_reps, dtype=np.float32)
@@ -124,7 +165,8 @@ class FaissFlatSearcher:
         if self._index is None:
             if not self._parts:
                 raise RuntimeError("FaissFlatSearcher: no vectors were added")
-            self._index = DenseIndex(np.concatenate(self._parts, axis=0), device=self._device)
+            self._index = DenseIndex(np.concatenate(self._parts, axis=0), device=self._device,
+                                     precision=self.precision)
         return self._index
 
     def search(self, q_reps, k):
@@ -154,6 +196,9 @@ def hybrid_search(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, 
     from . import _cabi
     from ._cabi import MSR_F_DROP_DF_EQ_N
 
+    if getattr(dense_index, "precision", "fp16") != "fp16":
+        raise ValueError("hybrid_search takes an fp16 DenseIndex (the reference's hybrid run uses --use_gpu, fp16 "
+                         f"storage); this one holds {dense_index.precision} rows")
     q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
     q16 = _as_fp16_rows(q_reps, dense_index.dim, dense_index)   # (consumed by the synchronous call below)
     nq = len(q_ptr) - 1

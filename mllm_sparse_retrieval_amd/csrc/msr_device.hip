@@ -667,6 +667,39 @@ static int batch_create_impl(msr_index* ix, const int64_t* q_ptr, const int32_t*
     return MSR_OK;
 }
 
+// Every field of a scoring launch over the whole batch (queries [0, nq), all of the handle's tiles, selection into
+// b->d_part, no diagnostics); the callers change what their launch does differently.
+void fill_score_args(ScoreArgs& sa, msr_batch* b, int k) {
+    msr_index* ix = b->ix;
+    DeviceIndex* d = ix->dev;
+    sa.seg_ptr = d->d_seg_ptr;
+    sa.postings = d->d_postings;
+    sa.q_meta = reinterpret_cast<const uint4*>(b->d_qptr);
+    sa.q_term = b->d_qterm;
+    sa.q_w = b->d_qw;
+    sa.dense = d->d_dense;
+    sa.q_dense = b->d_qdense;
+    sa.n_pairs = d->n_pairs;
+    sa.part = b->d_part;
+    sa.n_docs = ix->host.h->n_docs;
+    sa.vec_base = d->vec_base;
+    sa.n_terms = d->seg_terms;
+    sa.tile0 = ix->shard_tile0;
+    sa.nq = (uint32_t)b->nq;
+    sa.q0 = 0;
+    sa.qn = (uint32_t)b->nq;
+    sa.k = (uint32_t)k;
+    sa.dump = nullptr;
+    sa.theta = nullptr;
+    sa.tl0 = 0;
+    sa.unsorted = 0;
+    sa.tpr = 1;
+    sa.dump_add = 0;
+    sa.dbg = 0;
+    sa.stamps = nullptr;
+    sa.light = 0;
+}
+
 extern "C" {
 
 int msr_batch_create(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int kmax,
@@ -708,33 +741,8 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
         HIP_TRY(hipEventRecord(b->ev0, d->stream));
     }
     ScoreArgs sa;
-    sa.seg_ptr = d->d_seg_ptr;
-    sa.postings = d->d_postings;
-    sa.q_meta = reinterpret_cast<const uint4*>(b->d_qptr);
-    sa.q_term = b->d_qterm;
-    sa.q_w = b->d_qw;
-    sa.dense = d->d_dense;
-    sa.q_dense = b->d_qdense;
-    sa.n_pairs = d->n_pairs;
-    sa.part = b->d_part;
-    sa.n_docs = h->n_docs;
-    sa.vec_base = d->vec_base;
-    sa.n_terms = d->seg_terms;
-    sa.tile0 = ix->shard_tile0;
-    sa.nq = (uint32_t)b->nq;
-    sa.q0 = 0;
-    sa.qn = (uint32_t)b->nq;
-    sa.k = (uint32_t)k;
-    sa.dump = nullptr;
-    sa.theta = nullptr;
-    sa.tl0 = 0;
-    sa.unsorted = 0;
-    sa.tpr = 1;
-    sa.dump_add = 0;
-    {
-        static const bool no_light = getenv("MSR_NO_LIGHT") != nullptr;  // diagnostic: the general accumulation only
-        sa.light = (!no_light && b->max_sparse_terms <= 64) ? 1u : 0u;
-    }
+    fill_score_args(sa, b, k);
+    sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;
     {
         const char* dbg = getenv("MSR_DEBUG_FLAGS");
         sa.dbg = dbg ? (uint32_t)strtoul(dbg, nullptr, 0) : 0u;
@@ -753,12 +761,11 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
     // top-k. (A launch holds at most 65535 tiles in y; x = queries.)
     int rc = MSR_OK;
     const uint32_t nt = ix->shard_ntiles;
-    static const int stage_env = getenv("MSR_STAGE1_TILES") ? atoi(getenv("MSR_STAGE1_TILES")) : -1;
     uint32_t t1 = nt;
     // (small launches — fewer (tile, query) pairs than one round of resident workgroups — stay in ONE launch: two
     // more kernels in the chain would cost the call more latency than the cheaper selection saves)
-    if (nt >= 2 && !sa.dbg && stage_env != 0 && (stage_env > 0 || (uint64_t)nt * (uint64_t)b->nq >= kMinStagedPairs))
-        t1 = stage_env > 0 ? std::min<uint32_t>(nt, (uint32_t)stage_env) : std::max<uint32_t>(1u, nt / kStage1Fraction);
+    if (nt >= 2 && !sa.dbg && (uint64_t)nt * (uint64_t)b->nq >= kMinStagedPairs)
+        t1 = std::max<uint32_t>(1u, nt / kStage1Fraction);
     sa.theta = nullptr;
     sa.unsorted = (b->unsorted_ok && nt == 1) ? 1u : 0u;  // one tile: its list IS the query's list
     rc = launch_score(d->stream, h->tile_docs, 0, t1, sa);
@@ -1228,37 +1235,6 @@ static int ensure_buf(void** p, size_t* have, size_t want_elems, size_t elem_byt
     }
     *have = want_elems;
     return MSR_OK;
-}
-
-static void fill_score_args(ScoreArgs& sa, msr_batch* b, int k) {
-    msr_index* ix = b->ix;
-    DeviceIndex* d = ix->dev;
-    sa.seg_ptr = d->d_seg_ptr;
-    sa.postings = d->d_postings;
-    sa.q_meta = reinterpret_cast<const uint4*>(b->d_qptr);
-    sa.q_term = b->d_qterm;
-    sa.q_w = b->d_qw;
-    sa.dense = d->d_dense;
-    sa.q_dense = b->d_qdense;
-    sa.n_pairs = d->n_pairs;
-    sa.part = b->d_part;
-    sa.n_docs = ix->host.h->n_docs;
-    sa.vec_base = d->vec_base;
-    sa.n_terms = d->seg_terms;
-    sa.tile0 = ix->shard_tile0;
-    sa.nq = (uint32_t)b->nq;
-    sa.q0 = 0;
-    sa.qn = (uint32_t)b->nq;
-    sa.k = (uint32_t)k;
-    sa.dump = nullptr;
-    sa.theta = nullptr;
-    sa.tl0 = 0;
-    sa.unsorted = 0;
-    sa.tpr = 1;
-    sa.dump_add = 0;
-    sa.dbg = 0;
-    sa.stamps = nullptr;
-    sa.light = 0;
 }
 
 int msr_batch_search_termshard(msr_batch* b, int k) {

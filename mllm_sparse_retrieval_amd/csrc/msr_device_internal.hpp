@@ -212,3 +212,4 @@ struct msr_batch {
 void batch_free(msr_batch* b);          // release + unregister from the index + delete
 void batch_release_device(msr_batch* b); // device buffers and events only (the index is being closed)
 extern "C" int batch_search_local(msr_batch* b, int k, bool final_arrays);  // internal, not part of include/msr.h
+void fill_score_args(msr::ScoreArgs& sa, msr_batch* b, int k);  // a launch over the whole batch and every tile

@@ -26,9 +26,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 typedef float float4v __attribute__((ext_vector_type(4)));
 
-// LAB != 0 instantiations (scripts/gemm_lab.hip only, which defines MSR_GEMM_LAB) stamp the K loop of every block:
+// LAB != 0 instantiations (scripts/gemm_lab.hip only, which defines MSR_LAB_GEMM) stamp the K loop of every block:
 // shader cycles and 100 MHz ticks of the loop, the block's life (start, loop start, loop end, stores issued, stores done)
-#ifdef MSR_GEMM_LAB
+#ifdef MSR_LAB_GEMM
 __device__ uint64_t g_gemm_lab_stamps[8 * 4096];
 #else
 extern __device__ uint64_t g_gemm_lab_stamps[];  // never referenced by the LAB == 0 instantiations the library builds

@@ -1,7 +1,7 @@
-// Hybrid path and encode-side sparsifier: the dense fp16 MFMA scorers (the production 256 x 256 kernel lives in
-// msr_gemm_w4.hpp: dense_scores_256k; here the 128 x 128 kernel for small grids and two earlier 256 x 256 kernels kept
-// as diagnostics), the fused per-query kernel of single-tile indexes (hybrid_tiles), the reference's min-max fusion
-// for multi-tile indexes (fuse_tiles), the log1p-relu top-k sparsifier (sparsify_keys), and their C-ABI entry points.
+// Hybrid path and encode-side sparsifier: the dense fp16 MFMA scorers (the 256 x 256 kernel lives in msr_gemm_w4.hpp:
+// dense_scores_256k; here the 128 x 128 kernel for small grids), the fused per-query kernel of single-tile indexes
+// (hybrid_tiles), the reference's min-max fusion for multi-tile indexes (fuse_tiles), the log1p-relu top-k sparsifier
+// (sparsify_keys), and their C-ABI entry points.
 // Selection and list merging reuse the search path's kernels (launch_select / launch_merge, msr_device.hip).
 #include <chrono>
 #include <cmath>
@@ -110,262 +110,6 @@ __global__ __launch_bounds__(256) void dense_scores(const _Float16* __restrict__
 }
 
 
-// ---- (diagnostic, MSR_GEMM_NO_PIPE) the same product on a 256 x 256 block: 8 waves (2 x 4), each 128 x 64 = 4 x 2 MFMA tiles of 32 x 32 (six fragment
-// reads per eight MFMAs instead of four per four), K in steps of 64, two LDS stages of 2 x 32 KiB filled by LDS-DMA
-// (global_load_lds_dwordx4: no staging registers, no ds_write pass), one barrier per K step. The DMA writes LDS
-// lane-linear (wave-uniform base + 16 B x lane: eight 128-byte rows per instruction), so the bank swizzle goes on the
-// SOURCE address: the lane that fills 16-byte slot s of row `row` fetches the row's segment s ^ ((row >> 1) & 7), and
-// the fragment read of segment g of that row goes to slot g ^ ((row >> 1) & 7): 16 consecutive rows then touch 64
-// distinct banks. Used when the grid fills the chip (>= 256 blocks) and H % 64 == 0; otherwise the 128 x 128 kernel.
-constexpr int kG2Stage = 2 * 256 * 128;  // bytes per stage: A rows then B rows, 128 B (64 halves) each
-
-// Block -> tile map: a 2-D grid (x = query block, y = doc block) when `db_n` is 0; else a 1-D grid that is XCD-aware:
-// workgroup L runs on XCD L % 8 (round-robin dispatch) as that XCD's (L / 8)-th block, and every XCD walks its own
-// contiguous EIGHTH of the block list in patch-major order (patches of 8 query blocks x 4 doc blocks). The 32 blocks
-// resident together on an XCD (one per CU) are then one patch or the seam of two: per K step they share about 8 + 4
-// operand slabs of 32 KB through that XCD's L2 instead of fetching 2 x 32 — and all XCDs get the same number of blocks
-// (a patch grid dealt out patch by patch was 26 % SLOWER: 20 patches over 8 XCDs is 3 rounds for some, 2 for others).
-__global__ __launch_bounds__(512, 1) void dense_scores_256(const _Float16* __restrict__ Q, const _Float16* __restrict__ P,
-                                                           uint32_t* __restrict__ out, uint32_t M, uint32_t N, uint32_t H,
-                                                           uint64_t ld, uint32_t qb_n, uint32_t db_n, uint32_t raw) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // 2 stages
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t r = lane & 31, h = lane >> 5;
-    uint32_t qb = blockIdx.x, db = blockIdx.y;
-    if (db_n) {
-        const uint32_t n_blk = qb_n * db_n, per = (n_blk + 7u) / 8u;
-        const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-        const uint32_t t = xcd * per + slot;  // position in the patch-major order of all blocks
-        if (slot >= per || t >= n_blk) return;
-        const uint32_t pr = t / (8u * db_n), rem = t - pr * 8u * db_n;
-        const uint32_t hp = min(8u, qb_n - 8u * pr);  // query blocks in this patch row (the last one may be short)
-        const uint32_t pc = rem / (hp * 4u), rem2 = rem - pc * hp * 4u;
-        qb = pr * 8u + rem2 % hp;
-        db = pc * 4u + rem2 / hp;
-    }
-    const uint32_t q_blk = qb * 256, d_blk = db * 256;
-    if (d_blk >= N) {  // padding docs that select_tiles still reads: keys 0
-        for (uint32_t i = tid; i < 256 * 64; i += 512) {
-            const uint32_t q = q_blk + i / 64;
-            if (q < M) reinterpret_cast<uint4*>(out + (uint64_t)q * ld + d_blk)[i % 64] = make_uint4(0, 0, 0, 0);
-        }
-        return;
-    }
-    const uint32_t wm = (wave >> 2) * 128, wn = (wave & 3) * 64;
-    float16v acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    // LDS-DMA plan: instruction i of wave w fills rows 8c .. 8c+7 (c = 8i + w) of an operand; lane = (row in chunk, slot)
-    const _Float16* ga[4];
-    const _Float16* gb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t row = 8 * (8 * i + wave) + (lane >> 3);
-        const uint32_t seg = (lane & 7) ^ ((row >> 1) & 7);
-        ga[i] = Q + (uint64_t)(q_blk + row) * H + seg * 8;
-        gb[i] = P + (uint64_t)(d_blk + row) * H + seg * 8;
-    }
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef const __attribute__((address_space(1))) void glb_void;
-    auto issue = [&](int stage, uint32_t k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            uint8_t* const da = smem + stage * kG2Stage + (8 * i + wave) * 1024;
-            __builtin_amdgcn_global_load_lds((glb_void*)(ga[i] + k0), (lds_void*)da, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_void*)(gb[i] + k0), (lds_void*)(da + 256 * 128), 16, 0, 0);
-        }
-    };
-    const uint32_t f = (r >> 1) & 7;  // swizzle of this lane's fragment rows ((wm + 32 i + r) >> 1) & 7 == (r >> 1) & 7
-    const uint32_t fa = (wm + r) * 128, fb = 256 * 128 + (wn + r) * 128;
-    const uint32_t KT = H / 64;
-    issue(0, 0);
-    for (uint32_t kt = 0; kt < KT; ++kt) {
-        const int cur = (int)(kt & 1);
-        __syncthreads();  // (hipcc drains the DMA with vmcnt(0) first) stage `cur` is filled, stage cur^1 is free again
-        if (kt + 1 < KT) issue(cur ^ 1, (kt + 1) * 64);
-        const uint8_t* const st = smem + cur * kG2Stage;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const uint32_t slot = ((2 * kk + h) ^ f) * 16;
-            half8 a[4], b[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const half8*>(st + fa + i * 32 * 128 + slot);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const half8*>(st + fb + j * 32 * 128 + slot);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-    }
-    // C/D map of the 32x32 shapes: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t d = d_blk + wn + 32 * j + r;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t q = q_blk + wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (q < M) out[(uint64_t)q * ld + d] = d < N ? (raw ? __float_as_uint(acc[i][j][e]) : f32_to_key(acc[i][j][e])) : 0u;
-            }
-        }
-}
-
-// ---- (diagnostic since dense_scores_256k, MSR_GEMM_PINGPONG) the same 256 x 256 block with a DEEPER staging pipeline: K in sub-steps of 32 through FOUR LDS buffers of 32 KiB
-// (A: 256 rows x 64 B, B likewise), three sub-steps of LDS-DMA in flight while the fourth is consumed. The 2-buffer
-// kernel above drains its DMA with vmcnt(0) at every barrier and issues a whole K step's 8 DMAs per wave up front — at
-// 100-185 cycles of issue each that is ~1 200 cycles per wave and step during which neither wave of the SIMD feeds the
-// MFMA pipe (measured 46 % MFMA-busy cycles at 74 % L2 hit rate: not bandwidth). Here each sub-step issues 4 DMAs
-// per wave, waits with a COUNTED vmcnt (own pieces of the sub-step read next: 8 newer pieces stay in flight), uses
-// raw s_barriers (no fence, no vmcnt(0)), and runs the two waves of every SIMD in PING-PONG (see the loop):
-//     RAW: a sub-step's pieces are waited for by their issuing waves BEFORE the barrier the readers pass;
-//     WAR: a buffer is refilled after both groups' reads of it have returned (lgkmcnt(0) before the barrier in between).
-// Rows are 64 B = 4 slots of 16 B: the DMA writes LDS lane-linear (16 rows x 4 slots per instruction), so the bank
-// swizzle slot ^= (row >> 2) & 3 goes on the SOURCE address and again on the fragment reads (the four 16-lane groups
-// of a ds_read_b128 then touch 16 distinct 16-byte bank groups).
-constexpr int kGpStage = 2 * 256 * 64;  // bytes per sub-step buffer: A rows then B rows
-constexpr int kGpStages = 4;
-
-__global__ __launch_bounds__(512, 1) void dense_scores_256p(const _Float16* __restrict__ Q, const _Float16* __restrict__ P,
-                                                            uint32_t* __restrict__ out, uint32_t M, uint32_t N, uint32_t H,
-                                                            uint64_t ld, uint32_t qb_n, uint32_t db_n, uint32_t raw) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // 4 sub-step buffers (ONE LDS object)
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = rfl(tid >> 6);
-    const uint32_t r = lane & 31, h = lane >> 5;
-    uint32_t qb, db;
-    {   // XCD-aware patch-major order, as in dense_scores_256
-        const uint32_t n_blk = qb_n * db_n, per = (n_blk + 7u) / 8u;
-        const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-        const uint32_t t = xcd * per + slot;
-        if (slot >= per || t >= n_blk) return;
-        const uint32_t pr = t / (8u * db_n), rem = t - pr * 8u * db_n;
-        const uint32_t hp = min(8u, qb_n - 8u * pr);
-        const uint32_t pc = rem / (hp * 4u), rem2 = rem - pc * hp * 4u;
-        qb = pr * 8u + rem2 % hp;
-        db = pc * 4u + rem2 / hp;
-    }
-    const uint32_t q_blk = qb * 256, d_blk = db * 256;
-    if (d_blk >= N) {  // padding docs: keys 0
-        for (uint32_t i = tid; i < 256 * 64; i += 512) {
-            const uint32_t q = q_blk + i / 64;
-            if (q < M) reinterpret_cast<uint4*>(out + (uint64_t)q * ld + d_blk)[i % 64] = make_uint4(0, 0, 0, 0);
-        }
-        return;
-    }
-    const uint32_t wm = (wave >> 2) * 128, wn = (wave & 3) * 64;
-    float16v acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    // DMA plan: piece c (1 KiB = 16 rows x 64 B) of an operand's sub-step; wave w issues pieces w and w + 8. Source
-    // address = (block base + k: scalar) + (row, swizzled segment: a 32-bit byte offset per lane), so that stepping k
-    // costs scalar adds only (a block's rows span 256 x H x 2 B < 4 GiB)
-    const char* const qbase = reinterpret_cast<const char*>(Q + (uint64_t)q_blk * H);
-    const char* const pbase = reinterpret_cast<const char*>(P + (uint64_t)d_blk * H);
-    uint32_t voff[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const uint32_t row = 16 * (wave + 8 * i) + (lane >> 2);
-        const uint32_t seg = (lane & 3) ^ ((row >> 2) & 3);
-        voff[i] = row * H * 2 + seg * 16;
-    }
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef const __attribute__((address_space(1))) void glb_void;
-    auto issue = [&](uint32_t stage, uint32_t k0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint8_t* const da = smem + stage * kGpStage + (wave + 8 * i) * 1024;
-            __builtin_amdgcn_global_load_lds((glb_void*)(qbase + (uint64_t)k0 * 2 + voff[i]), (lds_void*)da, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_void*)(pbase + (uint64_t)k0 * 2 + voff[i]), (lds_void*)(da + 256 * 64), 16, 0, 0);
-        }
-    };
-    const uint32_t f = (r >> 2) & 3;  // swizzle of this lane's fragment rows: (wm + 32 i + r) >> 2 & 3 == (r >> 2) & 3
-    const uint32_t fa = (wm + r) * 64, fb = 256 * 64 + (wn + r) * 64;
-    const uint32_t KP = H / 32;
-    // PING-PONG: the workgroup's waves w and w + 4 share a SIMD (waves go to SIMDs cyclically); group 0 (waves 0-3) and
-    // group 1 (waves 4-7) run the same loop half a sub-step apart, so in every barrier interval one wave of each SIMD
-    // reads fragments / issues DMA while the other issues its 16 MFMAs:
-    //     interval 2p   : group 0 MEM(p)   | group 1 MFMA(p-1)
-    //     interval 2p+1 : group 0 MFMA(p)  | group 1 MEM(p)
-    // MEM(p) = 12 fragment reads of buffer p & 3, then the wave's 4 DMAs of sub-step p + 3 into buffer (p - 1) & 3 (both
-    // groups have read it: group 1 in interval 2p - 1, with lgkmcnt(0) before that interval's barrier). Before the barrier
-    // that ends an odd interval every wave waits (counted) for its own pieces of sub-step p + 1, which group 0 reads next.
-    // Measured with s_memtime laps (one block, 128 sub-steps, cycles per sub-step and wave): MEM 780 (fragment reads +
-    // DMA issue + lgkmcnt), counted vmcnt wait 300, MFMA issue 575, barriers 360 — 2 020 per sub-step for 1 024 cycles of
-    // MFMA per SIMD = the 52 % MFMA-busy the counters show, at a clock that sags to ~1.85 GHz under this load (2.55 GHz in
-    // the integer kernels). Moving 1, 2 or all 4 DMAs between the MFMAs shortens MEM by < 10 % and lengthens MFMA (908
-    // vs 949 TFLOP/s for all 4); without s_setprio 840; sixteen waves (4 x 4, 64 x 64 each, four per SIMD, one barrier
-    // per sub-step, no ping-pong) 857. What is left is the fragment-read phase itself and the DMA latency under load
-    // (~4 000 cycles: three sub-steps in flight do not quite cover it).
-    const uint32_t grp = wave >> 2;
-    auto bar = []() { asm volatile("s_barrier" ::: "memory"); };
-    auto wait_landed = [&](uint32_t p_next) {  // own pieces of sub-step p_next landed; newer ones (<= 2 sub-steps) stay in flight
-        const uint32_t newer = p_next + 2 < KP ? 2u : (p_next + 1 < KP ? 1u : 0u);
-        if (newer == 2)
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (newer == 1)
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    issue(0, 0);
-    if (KP > 1) issue(1, 32);
-    if (KP > 2) issue(2, 64);
-    wait_landed(0);
-    bar();
-    if (grp) bar();  // group 1 starts half a sub-step later
-    for (uint32_t p = 0; p < KP; ++p) {
-        // ---- MEM(p)
-        const uint8_t* const st = smem + (p & 3) * kGpStage;
-        half8 a[2][4], b[2][2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const uint32_t slot = ((2 * kk + h) ^ f) * 16;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[kk][i] = *reinterpret_cast<const half8*>(st + fa + i * 32 * 64 + slot);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[kk][j] = *reinterpret_cast<const half8*>(st + fb + j * 32 * 64 + slot);
-        }
-        if (p + 3 < KP) issue((p + 3) & 3, (p + 3) * 32);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the fragments are in registers: the buffer may be refilled
-        if (grp) wait_landed(p + 1);                        // (group 1's MEM is the odd interval)
-        bar();
-        // ---- MFMA(p)
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[kk][i], b[kk][j], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        if (!grp) wait_landed(p + 1);                       // (group 0's MFMA is the odd interval)
-        bar();
-    }
-    if (!grp) bar();  // every wave has passed the same number of barriers
-    // C/D map of the 32x32 shapes: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t d = d_blk + wn + 32 * j + r;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t q = q_blk + wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (q < M) out[(uint64_t)q * ld + d] = d < N ? (raw ? __float_as_uint(acc[i][j][e]) : f32_to_key(acc[i][j][e])) : 0u;
-            }
-        }
-}
-
 }  // namespace msr
 
 struct msr_dense {
@@ -385,7 +129,7 @@ struct msr_dense {
     // use and kept while the mapping stays the same
     _Float16* d_P_ord = nullptr;
     std::vector<uint32_t> ord_map;
-    bool lds_attr_set = false;  // dense_scores_256 needs the 128 KiB dynamic-LDS opt-in once per device
+    bool lds_attr_set = false;  // dense_scores_256k needs the 128 KiB dynamic-LDS opt-in once per device
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
     // grown: six hipMalloc / hipFree pairs of up to 200 MB cost a call more than its kernels
     enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_COUNT };
@@ -408,6 +152,47 @@ struct msr_dense {
     }
 };
 
+// The part of msr_dense_open / msr_dense_open_f32 after their argument checks: the device check, a handle with its tile
+// geometry and stream, and zeroed device rows (d_P, or d_P32 with K padded to hp) into which `upload(dx)` copies the n
+// given rows.
+template <class Upload>
+static int dense_open(uint64_t n, uint32_t h, bool f32, int device, Upload upload, msr_dense** out) {
+    int n_dev = 0;
+    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
+        set_error("no usable HIP device %d; there is no CPU dense search path", device);
+        return MSR_E_NODEVICE;
+    }
+    msr_dense* dx = new (std::nothrow) msr_dense;
+    if (!dx) {
+        set_error("out of host memory");
+        return MSR_E_NOMEM;
+    }
+    dx->device = device;
+    dx->n = n;
+    dx->h = h;
+    dx->f32 = f32;
+    if (f32) dx->hp = (h + kF32KStep - 1) / kF32KStep * kF32KStep;  // zero columns: exactly neutral in the fmaf chain
+    dx->tile_docs = n <= 4096 ? 4096 : 8192;
+    dx->n_tiles = (uint32_t)std::max<uint64_t>((n + dx->tile_docs - 1) / dx->tile_docs, 1);
+    dx->n_pad = (uint64_t)dx->n_tiles * dx->tile_docs;
+    const size_t bytes = (size_t)dx->n_pad * (f32 ? (size_t)dx->hp * 4 : (size_t)h * 2);
+    void* rows = nullptr;
+    const bool ok = hipSetDevice(device) == hipSuccess &&
+                    hipStreamCreateWithFlags(&dx->stream, hipStreamNonBlocking) == hipSuccess &&
+                    hipMalloc(&rows, bytes) == hipSuccess;
+    if (f32)
+        dx->d_P32 = (float*)rows;
+    else
+        dx->d_P = (_Float16*)rows;
+    if (!ok || hipMemset(rows, 0, bytes) != hipSuccess || (n && upload(dx) != hipSuccess)) {
+        set_error("device setup of the %sdense index failed (%zu bytes)", f32 ? "f32 " : "", bytes);
+        msr_dense_close(dx);
+        return MSR_E_HIP;
+    }
+    *out = dx;
+    return MSR_OK;
+}
+
 extern "C" {
 
 int msr_dense_open(const uint16_t* p_fp16, uint64_t n, uint32_t h, int device, msr_dense** out) {
@@ -421,34 +206,9 @@ int msr_dense_open(const uint16_t* p_fp16, uint64_t n, uint32_t h, int device, m
                   (unsigned long long)n, h);
         return MSR_E_INVAL;
     }
-    int n_dev = 0;
-    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-        set_error("no usable HIP device %d; there is no CPU dense search path", device);
-        return MSR_E_NODEVICE;
-    }
-    msr_dense* dx = new (std::nothrow) msr_dense;
-    if (!dx) {
-        set_error("out of host memory");
-        return MSR_E_NOMEM;
-    }
-    dx->device = device;
-    dx->n = n;
-    dx->h = h;
-    dx->tile_docs = n <= 4096 ? 4096 : 8192;
-    dx->n_tiles = (uint32_t)std::max<uint64_t>((n + dx->tile_docs - 1) / dx->tile_docs, 1);
-    dx->n_pad = (uint64_t)dx->n_tiles * dx->tile_docs;
-    const size_t bytes = (size_t)dx->n_pad * h * 2;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&dx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&dx->d_P, bytes) != hipSuccess || hipMemset(dx->d_P, 0, bytes) != hipSuccess ||
-        (n && hipMemcpy(dx->d_P, p_fp16, (size_t)n * h * 2, hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("device setup of the dense index failed (%zu bytes)", bytes);
-        if (dx->d_P) (void)hipFree(dx->d_P);
-        if (dx->stream) (void)hipStreamDestroy(dx->stream);
-        delete dx;
-        return MSR_E_HIP;
-    }
-    *out = dx;
-    return MSR_OK;
+    return dense_open(n, h, false, device, [&](const msr_dense* dx) {
+        return hipMemcpy(dx->d_P, p_fp16, (size_t)n * h * 2, hipMemcpyHostToDevice);
+    }, out);
 }
 
 int msr_dense_open_f32(const float* p, uint64_t n, uint32_t h, int device, msr_dense** out) {
@@ -462,36 +222,9 @@ int msr_dense_open_f32(const float* p, uint64_t n, uint32_t h, int device, msr_d
                   (unsigned long long)n, h);
         return MSR_E_INVAL;
     }
-    int n_dev = 0;
-    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-        set_error("no usable HIP device %d; there is no CPU dense search path", device);
-        return MSR_E_NODEVICE;
-    }
-    msr_dense* dx = new (std::nothrow) msr_dense;
-    if (!dx) {
-        set_error("out of host memory");
-        return MSR_E_NOMEM;
-    }
-    dx->device = device;
-    dx->n = n;
-    dx->h = h;
-    dx->f32 = true;
-    dx->hp = (h + kF32KStep - 1) / kF32KStep * kF32KStep;  // zero columns: exactly neutral in the fmaf chain
-    dx->tile_docs = n <= 4096 ? 4096 : 8192;
-    dx->n_tiles = (uint32_t)std::max<uint64_t>((n + dx->tile_docs - 1) / dx->tile_docs, 1);
-    dx->n_pad = (uint64_t)dx->n_tiles * dx->tile_docs;
-    const size_t bytes = (size_t)dx->n_pad * dx->hp * 4;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&dx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&dx->d_P32, bytes) != hipSuccess || hipMemset(dx->d_P32, 0, bytes) != hipSuccess ||
-        (n && hipMemcpy2D(dx->d_P32, (size_t)dx->hp * 4, p, (size_t)h * 4, (size_t)h * 4, n, hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("device setup of the f32 dense index failed (%zu bytes)", bytes);
-        if (dx->d_P32) (void)hipFree(dx->d_P32);
-        if (dx->stream) (void)hipStreamDestroy(dx->stream);
-        delete dx;
-        return MSR_E_HIP;
-    }
-    *out = dx;
-    return MSR_OK;
+    return dense_open(n, h, true, device, [&](const msr_dense* dx) {
+        return hipMemcpy2D(dx->d_P32, (size_t)dx->hp * 4, p, (size_t)h * 4, (size_t)h * 4, n, hipMemcpyHostToDevice);
+    }, out);
 }
 
 void msr_dense_close(msr_dense* dx) {
@@ -530,10 +263,6 @@ static int launch_dense_gemm(msr_dense* dx, const _Float16* P, const _Float16* d
     const bool big = dx->h % 64 == 0 && n_cover % 256 == 0 &&
                      (force_256 || (uint64_t)(qn_pad / 256) * (n_cover / 256) >= 256);
     if (big && !dx->lds_attr_set) {  // 128 KiB of dynamic LDS needs the opt-in (per device: kept in the handle)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(dense_scores_256),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kG2Stage));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(dense_scores_256p),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kGpStages * kGpStage));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(dense_scores_256k<0>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kGkStage));
         dx->lds_attr_set = true;
@@ -542,27 +271,14 @@ static int launch_dense_gemm(msr_dense* dx, const _Float16* P, const _Float16* d
     for (uint64_t d0 = 0; d0 < n_cover; d0 += blk * kMaxGridY) {
         const uint64_t nd = std::min<uint64_t>(n_cover - d0, blk * kMaxGridY);
         const uint32_t n_left = dx->n > d0 ? (uint32_t)std::min<uint64_t>(dx->n - d0, 0xFFFFFFFFull) : 0u;
-        static const bool no_patch = getenv("MSR_GEMM_NO_PATCH") != nullptr;  // diagnostic: the plain 2-D grid
-        static const bool no_pipe = getenv("MSR_GEMM_NO_PIPE") != nullptr;    // diagnostic: the 2-buffer kernel
-        static const bool pingpong = getenv("MSR_GEMM_PINGPONG") != nullptr;  // diagnostic: the 8-wave ping-pong kernel
-        if (big && !no_patch && !no_pipe && !pingpong) {
+        if (big) {
             const uint32_t qb_n = qn_pad / 256, db_n = (uint32_t)(nd / 256);
             hipLaunchKernelGGL(dense_scores_256k<0>, dim3((qb_n * db_n + 7) / 8 * 8), dim3(256), 2 * kGkStage, st, d_Q,
                                P + d0 * dx->h, d_S + d0, qn, n_left, dx->h, ld, qb_n, db_n, raw ? 1u : 0u);
-        } else if (big && !no_patch && !no_pipe) {
-            const uint32_t qb_n = qn_pad / 256, db_n = (uint32_t)(nd / 256);
-            hipLaunchKernelGGL(dense_scores_256p, dim3((qb_n * db_n + 7) / 8 * 8), dim3(512), kGpStages * kGpStage, st, d_Q,
-                               P + d0 * dx->h, d_S + d0, qn, n_left, dx->h, ld, qb_n, db_n, raw ? 1u : 0u);
-        } else if (big && !no_patch) {
-            const uint32_t qb_n = qn_pad / 256, db_n = (uint32_t)(nd / 256);
-            hipLaunchKernelGGL(dense_scores_256, dim3((qb_n * db_n + 7) / 8 * 8), dim3(512), 2 * kG2Stage, st, d_Q,
-                               P + d0 * dx->h, d_S + d0, qn, n_left, dx->h, ld, qb_n, db_n, raw ? 1u : 0u);
-        } else if (big)
-            hipLaunchKernelGGL(dense_scores_256, dim3(qn_pad / 256, (uint32_t)(nd / 256)), dim3(512), 2 * kG2Stage, st, d_Q,
-                               P + d0 * dx->h, d_S + d0, qn, n_left, dx->h, ld, 0u, 0u, raw ? 1u : 0u);
-        else
+        } else {
             hipLaunchKernelGGL(dense_scores, dim3(qn_pad / 128, (uint32_t)(nd / 128)), dim3(256), 0, st, d_Q, P + d0 * dx->h,
                                d_S + d0, qn, n_left, dx->h, ld, raw ? 1u : 0u);
+        }
         HIP_TRY(hipGetLastError());
     }
     return MSR_OK;
@@ -1739,6 +1455,83 @@ static int ensure_ordinal_rows(msr_dense* dx, hipStream_t stream, const uint32_t
     return MSR_OK;
 }
 
+// diagnostic (MSR_DEBUG_HYBRID): phase clocks of the hybrid kernels, host laps, chunking and second-round counts
+static bool debug_hybrid() {
+    static const bool on = getenv("MSR_DEBUG_HYBRID") != nullptr;
+    return on;
+}
+
+// Score rows per chunk of queries of the two device-resident hybrid paths: the kernel after the GEMM reads its rows
+// back out of the Infinity Cache (80 to 1 024 MB measured within noise of each other)
+constexpr uint64_t kHybridChunkBytes = 160ull << 20;
+
+// What the fused and the multi-tile path share before their launches
+struct HybridSetup {
+    msr_batch* b = nullptr;
+    _Float16* d_Q = nullptr;  // [nq rounded up to 256][h] queries, zero padded
+    uint32_t* d_S = nullptr;  // score rows of one chunk
+    bool ok = false;          // every scratch slot was taken and every upload enqueued
+    ScoreArgs sa;             // every query of the batch; the hybrid kernels write their lists through ha
+    HybridArgs ha;            // the fields that both paths use
+};
+
+// The ordinal-ordered passage rows, the query batch (created for `batch_k`), the query matrix, `s_bytes` of score rows
+// and the result lists out of the handle's scratch, the uploads of the queries and of self_ord, and both argument
+// blocks. A non-zero return is an error before the batch exists; s.ok == false is a failed slot or upload (the caller
+// reports it and still owns s.b). `lap(what)` marks the host laps of the steps.
+template <class Lap>
+static int hybrid_setup(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                        const uint16_t* q_fp16, int nq, int batch_k, int depth, int k, float alpha, uint32_t flags,
+                        const uint32_t* row2ord, const int32_t* self_ord, uint64_t ld, size_t s_bytes, Lap&& lap,
+                        HybridSetup& s) {
+    DeviceIndex* d = ix->dev;
+    if (int rc = ensure_ordinal_rows(dx, d->stream, row2ord, ix->host.h->n_docs)) return rc;
+    lap("ordinal map");
+    if (int rc = msr_batch_create(ix, q_ptr, q_term, q_w, nq, batch_k, flags, &s.b)) return rc;
+    lap("sparse batch");
+    const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
+    const size_t perk = std::max<size_t>((size_t)nq * k, 1);
+    s.d_Q = (_Float16*)dx->take(msr_dense::S_Q, std::max<size_t>((size_t)nq_pad * dx->h * 2, 16));
+    s.d_S = (uint32_t*)dx->take(msr_dense::S_S, s_bytes);
+    uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perk * 4);
+    float* d_sf = (float*)dx->take(msr_dense::S_SF, perk * 4);
+    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_N, std::max<size_t>(nq, 1) * 4);
+    int32_t* d_self = nullptr;
+    bool ok = s.d_Q && s.d_S && d_ord && d_sf && d_n;
+    if (ok && self_ord)
+        ok = (d_self = (int32_t*)dx->take(msr_dense::S_SELF, std::max<size_t>(nq, 1) * 4)) != nullptr &&
+             hipMemcpyAsync(d_self, self_ord, (size_t)nq * 4, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+    if (ok && nq)
+        ok = hipMemsetAsync(s.d_Q + (size_t)nq * dx->h, 0, (size_t)(nq_pad - nq) * dx->h * 2, d->stream) == hipSuccess &&
+             hipMemcpyAsync(s.d_Q, q_fp16, (size_t)nq * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+    s.ok = ok;
+    fill_score_args(s.sa, s.b, k);
+    s.sa.part = nullptr;
+    HybridArgs& ha = s.ha;
+    ha.dkeys = s.d_S;
+    ha.ld = ld;
+    ha.self_ord = d_self;
+    ha.depth = (uint32_t)depth;
+    ha.k = (uint32_t)k;
+    ha.w_dense = alpha;
+    ha.w_sparse = 1.0f - alpha;
+    ha.out_ord = d_ord;
+    ha.out_score = d_sf;
+    ha.out_n = d_n;
+    return MSR_OK;
+}
+
+// the result lists of a hybrid call back to the host
+static int hybrid_download(const HybridArgs& ha, int nq, int k, uint32_t* out_ord, float* out_score, int32_t* out_n) {
+    if (nq && (hipMemcpy(out_ord, ha.out_ord, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+               hipMemcpy(out_score, ha.out_score, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+               hipMemcpy(out_n, ha.out_n, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_error("download failed in msr_hybrid_search");
+        return MSR_E_HIP;
+    }
+    return MSR_OK;
+}
+
 // The fused path of msr_hybrid_search (single-tile indexes, k <= 64): per chunk of queries (normally ONE chunk) a GEMM
 // launch on the ordinal-permuted passage matrix, then hybrid_tiles. ms = {fused scoring + selection + fusion kernel, dense GEMM, 0, 0}.
 static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
@@ -1750,101 +1543,43 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     const uint64_t n = h->n_docs;
     HIP_TRY(hipSetDevice(d->device));
     // diagnostic (MSR_DEBUG_HYBRID): host-side laps of the call, printed with the kernel span
-    static const bool dbg_host = getenv("MSR_DEBUG_HYBRID") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
     char laps[512];
     size_t laps_n = 0;
     laps[0] = 0;
     auto lap = [&](const char* what) {
-        if (!dbg_host) return;
+        if (!debug_hybrid()) return;
         const auto now = std::chrono::steady_clock::now();
         const double msx = std::chrono::duration<double, std::milli>(now - t_last).count();
         t_last = now;
         if (laps_n < sizeof(laps)) laps_n += (size_t)snprintf(laps + laps_n, sizeof(laps) - laps_n, " %s %.2f", what, msx);
     };
-    if (int rc0 = ensure_ordinal_rows(dx, d->stream, row2ord, n)) return rc0;
-    lap("ordinal map");
-    msr_batch* b = nullptr;
-    int rc = msr_batch_create(ix, q_ptr, q_term, q_w, nq, k, flags, &b);
-    if (rc != MSR_OK) return rc;
-    lap("sparse batch");
     const uint32_t nt_threads = h->tile_docs == 4096 ? 256u : 512u;
     const uint64_t ld = (n + 4 * nt_threads - 1) / (4 * nt_threads) * (4 * nt_threads);  // whole select rounds
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (n + 255) / 256 * 256);
     const uint32_t col_blocks = (uint32_t)(n_cover / 256);
-    // queries per chunk: everything when the score rows fit 2 GiB (one GEMM launch: the least tail and launch gaps; the
-    // round trip of the rows through HBM is ~0.25 GB per 6 400 queries — noise next to either kernel), else chunks of
-    // whole rounds of the chip's 256 CUs worth of 256 x 256 blocks
     const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
     // queries per chunk: whole rounds of the chip's 256 CUs worth of 256 x 256 GEMM blocks, score rows <= ~160 MB so
     // that hybrid_tiles finds its row in the Infinity Cache (the row load is a dependent fetch at the start of the
     // epilogue: from HBM the same kernel measured 1.66 ms instead of 1.30 ms per 25 010 queries)
-    static const uint64_t chunk_mb = getenv("MSR_HYBRID_CHUNK_MB") ? strtoull(getenv("MSR_HYBRID_CHUNK_MB"), nullptr, 0) : 160ull;  // diagnostic
-    uint64_t row_blocks = std::max<uint64_t>(1, (std::max<uint64_t>(chunk_mb, 1) << 20) / (ld * 4 * 256));
+    uint64_t row_blocks = std::max<uint64_t>(1, kHybridChunkBytes / (ld * 4 * 256));
     if (col_blocks && row_blocks * col_blocks >= 256) row_blocks = row_blocks * col_blocks / 256 * 256 / col_blocks;
     const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * 256, std::max<uint32_t>(nq_pad, 256u));
-    _Float16* d_Q = nullptr;
-    uint32_t* d_S = nullptr;
-    uint32_t* d_ord = nullptr;
-    float* d_sf = nullptr;
-    int32_t *d_n = nullptr, *d_self = nullptr;
-    std::vector<hipEvent_t> ev;
-    unsigned long long* d_stamps = nullptr;  // diagnostic (MSR_DEBUG_HYBRID): phase clocks of wave 0
-    if (getenv("MSR_DEBUG_HYBRID") && hipMalloc(&d_stamps, 8 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemsetAsync(d_stamps, 0, 8 * sizeof(unsigned long long), d->stream);
-    const size_t perk = std::max<size_t>((size_t)nq * k, 1);
-    d_Q = (_Float16*)dx->take(msr_dense::S_Q, std::max<size_t>((size_t)nq_pad * dx->h * 2, 16));
-    d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)qc * ld * 4);
-    d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perk * 4);
-    d_sf = (float*)dx->take(msr_dense::S_SF, perk * 4);
-    d_n = (int32_t*)dx->take(msr_dense::S_N, std::max<size_t>(nq, 1) * 4);
-    bool ok = d_Q && d_S && d_ord && d_sf && d_n;
-    if (ok && self_ord)
-        ok = (d_self = (int32_t*)dx->take(msr_dense::S_SELF, std::max<size_t>(nq, 1) * 4)) != nullptr &&
-             hipMemcpyAsync(d_self, self_ord, (size_t)nq * 4, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-    if (ok && nq)
-        ok = hipMemsetAsync(d_Q + (size_t)nq * dx->h, 0, (size_t)(nq_pad - nq) * dx->h * 2, d->stream) == hipSuccess &&
-             hipMemcpyAsync(d_Q, q_fp16, (size_t)nq * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-    if (!ok) {
+    HybridSetup s;
+    if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, k, depth, k, alpha, flags, row2ord, self_ord, ld,
+                               (size_t)qc * ld * 4, lap, s))
+        return rc0;
+    ScoreArgs& sa = s.sa;
+    const HybridArgs& ha = s.ha;
+    int rc = MSR_OK;
+    if (!s.ok) {
         set_error("device allocation or query upload failed in msr_hybrid_search (%u queries per chunk)", qc);
         rc = MSR_E_NOMEM;
     }
-    ScoreArgs sa;
-    sa.seg_ptr = d->d_seg_ptr;
-    sa.postings = d->d_postings;
-    sa.q_meta = reinterpret_cast<const uint4*>(b->d_qptr);
-    sa.q_term = b->d_qterm;
-    sa.q_w = b->d_qw;
-    sa.dense = d->d_dense;
-    sa.q_dense = b->d_qdense;
-    sa.n_pairs = d->n_pairs;
-    sa.part = nullptr;
-    sa.theta = nullptr;
-    sa.unsorted = 0;
-    sa.n_docs = n;
-    sa.vec_base = d->vec_base;
-    sa.n_terms = d->seg_terms;
-    sa.tile0 = 0;
-    sa.tl0 = 0;
-    sa.nq = (uint32_t)nq;
-    sa.k = (uint32_t)k;
-    sa.dump = nullptr;
-    sa.tpr = 1;
-    sa.dump_add = 0;
-    sa.dbg = 0;
-    sa.stamps = nullptr;
-    sa.light = 0;
-    HybridArgs ha;
-    ha.dkeys = d_S;
-    ha.ld = ld;
-    ha.self_ord = d_self;
-    ha.depth = (uint32_t)depth;
-    ha.k = (uint32_t)k;
-    ha.w_dense = alpha;
-    ha.w_sparse = 1.0f - alpha;
-    ha.out_ord = d_ord;
-    ha.out_score = d_sf;
-    ha.out_n = d_n;
+    std::vector<hipEvent_t> ev;
+    unsigned long long* d_stamps = nullptr;  // diagnostic (MSR_DEBUG_HYBRID): phase clocks of wave 0
+    if (debug_hybrid() && hipMalloc(&d_stamps, 8 * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemsetAsync(d_stamps, 0, 8 * sizeof(unsigned long long), d->stream);
     static const bool inner_events = getenv("MSR_HYBRID_NO_INNER_EVENTS") == nullptr;
     lap("alloc + enqueue uploads");
     hipEvent_t e_all[2] = {nullptr, nullptr};
@@ -1866,7 +1601,8 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
             break;
         }
         if (inner_events) (void)hipEventRecord(e[0], d->stream);
-        rc = launch_dense_gemm(dx, dx->d_P_ord, d_Q + (size_t)q0 * dx->h, d_S, qn, qn_pad, n_cover, ld, d->stream, true, true);
+        rc = launch_dense_gemm(dx, dx->d_P_ord, s.d_Q + (size_t)q0 * dx->h, s.d_S, qn, qn_pad, n_cover, ld, d->stream, true,
+                               true);
         if (rc != MSR_OK) break;
         if (inner_events) (void)hipEventRecord(e[1], d->stream);
         sa.q0 = q0;
@@ -1892,7 +1628,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     }
     float t_gemm = 0, t_fused = 0, t_all = 0;
     if (rc == MSR_OK) (void)hipEventElapsedTime(&t_all, e_all[0], e_all[1]);
-    if (getenv("MSR_DEBUG_HYBRID")) fprintf(stderr, "[msr] hybrid pipeline span %.3f ms (inner events %d)\n", t_all, (int)inner_events);
+    if (debug_hybrid()) fprintf(stderr, "[msr] hybrid pipeline span %.3f ms (inner events %d)\n", t_all, (int)inner_events);
     lap("uploads + kernels");
     if (rc == MSR_OK) {
         // (only the per-chunk laps depend on the inner events; the results are downloaded either way)
@@ -1904,12 +1640,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
             t_fused += c;
         }
         if (!inner_events) t_fused = t_all;  // the span is all there is: reported as the fused kernel's slot
-        if (nq && (hipMemcpy(out_ord, d_ord, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(out_score, d_sf, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(out_n, d_n, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-            set_error("download failed in msr_hybrid_search");
-            rc = MSR_E_HIP;
-        }
+        rc = hybrid_download(ha, nq, k, out_ord, out_score, out_n);
     }
     lap("download");
     if (ms) {
@@ -1929,10 +1660,10 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
         if (x) (void)hipEventDestroy(x);
     for (hipEvent_t x : e_all)
         if (x) (void)hipEventDestroy(x);
-    // (d_Q, d_S, d_ord, d_sf, d_n, d_self stay with the dense handle for the next call)
-    batch_free(b);
+    // (the scratch stays with the dense handle for the next call)
+    batch_free(s.b);
     lap("free");
-    if (dbg_host) fprintf(stderr, "[msr] hybrid host laps (ms):%s\n", laps);
+    if (debug_hybrid()) fprintf(stderr, "[msr] hybrid host laps (ms):%s\n", laps);
     return rc;
 }
 
@@ -1962,21 +1693,15 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     const uint64_t n = h->n_docs;
     const uint32_t tile = h->tile_docs, n_tiles = h->n_tiles;
     HIP_TRY(hipSetDevice(d->device));
-    if (int rc0 = ensure_ordinal_rows(dx, d->stream, row2ord, n)) return rc0;
-    msr_batch* b = nullptr;
-    int rc = msr_batch_create(ix, q_ptr, q_term, q_w, nq, 1, flags, &b);  // (only the query arrays are used)
-    if (rc != MSR_OK) return rc;
     const uint64_t ld = (uint64_t)n_tiles * tile;  // a query's score row: tile t starts at column t * tile
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (n + 255) / 256 * 256);
     const uint32_t col_blocks = (uint32_t)(n_cover / 256);
     const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
     // queries per chunk: score rows of ~160 MB (they are read back out of the Infinity Cache), whole rounds of the
-    // chip's 256 CUs worth of GEMM blocks
-    static const uint64_t chunk_mb = getenv("MSR_HYBRID_CHUNK_MB") ? strtoull(getenv("MSR_HYBRID_CHUNK_MB"), nullptr, 0) : 160ull;
-    // (the bytes that travel are the n_cover written columns of a row, not its padded stride). Among the chunk sizes
-    // that fit, the one whose GEMM grid fills its last round of 256 CUs best: 2 x 98 blocks leave a quarter of the chip
-    // idle, 5 x 98 = 490 fill 1.91 rounds
-    const uint64_t rb_max = std::max<uint64_t>(1, (std::max<uint64_t>(chunk_mb, 1) << 20) / (std::max<uint64_t>(n_cover, 256) * 4 * 256));
+    // chip's 256 CUs worth of GEMM blocks (the bytes that travel are the n_cover written columns of a row, not its
+    // padded stride). Among the chunk sizes that fit, the one whose GEMM grid fills its last round of 256 CUs best:
+    // 2 x 98 blocks leave a quarter of the chip idle, 5 x 98 = 490 fill 1.91 rounds
+    const uint64_t rb_max = std::max<uint64_t>(1, kHybridChunkBytes / (std::max<uint64_t>(n_cover, 256) * 4 * 256));
     const uint64_t row_blocks = pick_row_blocks(col_blocks, rb_max, nq_pad / 256);
     const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * 256, std::max<uint32_t>(nq_pad, 256u));
     const uint64_t last_docs = n - (uint64_t)(n_tiles - 1) * tile;
@@ -1986,64 +1711,22 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     const size_t per_tile_row = (size_t)n_tiles;
     // record slots (a tile's union of two candidate sets: 2 x quota): a chunk of the first round or at least ONE row of the second
     const size_t cand_slots = 2 * std::max<size_t>((size_t)qc * per_tile_row * quota_full, per_tile_row * (size_t)depth);
-    const size_t perk = std::max<size_t>((size_t)nq * k, 1);
-    _Float16* d_Q = (_Float16*)dx->take(msr_dense::S_Q, std::max<size_t>((size_t)nq_pad * dx->h * 2, 16));
-    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)qc * ld * 4);
-    uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perk * 4);
-    float* d_sf = (float*)dx->take(msr_dense::S_SF, perk * 4);
-    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_N, std::max<size_t>(nq, 1) * 4);
+    HybridSetup s;  // (a batch for k = 1: only its query arrays are used)
+    if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, 1, depth, k, alpha, flags, row2ord, self_ord, ld,
+                               (size_t)qc * ld * 4, [](const char*) {}, s))
+        return rc0;
+    ScoreArgs& sa = s.sa;
+    HybridArgs& ha = s.ha;
     uint32_t* d_rec = (uint32_t*)dx->take(msr_dense::S_CS, cand_slots * 12);  // ordinals | sparse scores | dense keys
     uint4* d_meta = (uint4*)dx->take(msr_dense::S_META, std::max<size_t>((size_t)qc * per_tile_row * 2 * 16, 32));
     uint32_t* d_flags = (uint32_t*)dx->take(msr_dense::S_FLAGS, std::max<size_t>(nq, 1) * 4);
     uint32_t* d_qlist = (uint32_t*)dx->take(msr_dense::S_QLIST, std::max<size_t>(nq, 1) * 4);
-    int32_t* d_self = nullptr;
-    bool ok = d_Q && d_S && d_ord && d_sf && d_n && d_rec && d_meta && d_flags && d_qlist;
-    if (ok && self_ord)
-        ok = (d_self = (int32_t*)dx->take(msr_dense::S_SELF, std::max<size_t>(nq, 1) * 4)) != nullptr &&
-             hipMemcpyAsync(d_self, self_ord, (size_t)nq * 4, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-    if (ok && nq)
-        ok = hipMemsetAsync(d_Q + (size_t)nq * dx->h, 0, (size_t)(nq_pad - nq) * dx->h * 2, d->stream) == hipSuccess &&
-             hipMemcpyAsync(d_Q, q_fp16, (size_t)nq * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+    bool ok = s.ok && d_rec && d_meta && d_flags && d_qlist;
+    int rc = MSR_OK;
     if (!ok) {
         set_error("device allocation or query upload failed in msr_hybrid_search (%u queries per chunk, %u tiles)", qc, n_tiles);
         rc = MSR_E_NOMEM;
     }
-    ScoreArgs sa;
-    sa.seg_ptr = d->d_seg_ptr;
-    sa.postings = d->d_postings;
-    sa.q_meta = reinterpret_cast<const uint4*>(b->d_qptr);
-    sa.q_term = b->d_qterm;
-    sa.q_w = b->d_qw;
-    sa.dense = d->d_dense;
-    sa.q_dense = b->d_qdense;
-    sa.n_pairs = d->n_pairs;
-    sa.part = nullptr;
-    sa.theta = nullptr;
-    sa.unsorted = 0;
-    sa.n_docs = n;
-    sa.vec_base = d->vec_base;
-    sa.n_terms = d->seg_terms;
-    sa.tile0 = 0;
-    sa.tl0 = 0;
-    sa.nq = (uint32_t)nq;
-    sa.k = (uint32_t)k;
-    sa.dump = nullptr;
-    sa.tpr = 1;
-    sa.dump_add = 0;
-    sa.dbg = 0;
-    sa.stamps = nullptr;
-    sa.light = 0;
-    HybridArgs ha;
-    ha.dkeys = d_S;
-    ha.ld = ld;
-    ha.self_ord = d_self;
-    ha.depth = (uint32_t)depth;
-    ha.k = (uint32_t)k;
-    ha.w_dense = alpha;
-    ha.w_sparse = 1.0f - alpha;
-    ha.out_ord = d_ord;
-    ha.out_score = d_sf;
-    ha.out_n = d_n;
     ha.qlist = nullptr;
     ha.rec_ord = d_rec;
     ha.rec_s = d_rec + cand_slots;
@@ -2055,7 +1738,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     ha.quota_last = quota_last;
     ha.flags = d_flags;
     unsigned long long* d_fq = nullptr;
-    if (getenv("MSR_DEBUG_HYBRID") && hipMalloc(&d_fq, 16 * sizeof(unsigned long long)) == hipSuccess) {
+    if (debug_hybrid() && hipMalloc(&d_fq, 16 * sizeof(unsigned long long)) == hipSuccess) {
         (void)hipMemsetAsync(d_fq, 0, 16 * sizeof(unsigned long long), d->stream);
         ha.fq_stamps = d_fq;
     }
@@ -2063,7 +1746,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     auto launch_rows = [&](const _Float16* d_Qrows, uint32_t rows, uint32_t q0, hipEvent_t* e) -> int {
         const uint32_t rows_pad = (rows + 255) / 256 * 256;
         if (e) (void)hipEventRecord(e[0], d->stream);
-        int r2 = launch_dense_gemm(dx, dx->d_P_ord, d_Qrows, d_S, rows, rows_pad, n_cover, ld, d->stream, true, true);
+        int r2 = launch_dense_gemm(dx, dx->d_P_ord, d_Qrows, s.d_S, rows, rows_pad, n_cover, ld, d->stream, true, true);
         if (r2 != MSR_OK) return r2;
         if (e) (void)hipEventRecord(e[1], d->stream);
         sa.q0 = q0;
@@ -2125,7 +1808,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
             rc = MSR_E_HIP;
             break;
         }
-        rc = launch_rows(d_Q + (size_t)q0 * dx->h, qn, q0, e);
+        rc = launch_rows(s.d_Q + (size_t)q0 * dx->h, qn, q0, e);
     }
     std::vector<uint32_t> hflags((size_t)nq, 0);
     if (rc == MSR_OK && nq &&
@@ -2138,9 +1821,9 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     std::vector<uint32_t> redo;
     for (int i = 0; i < nq && rc == MSR_OK; ++i)
         if (hflags[(size_t)i]) redo.push_back((uint32_t)i);
-    static const bool dbg = getenv("MSR_DEBUG_HYBRID") != nullptr;
-    if (dbg) fprintf(stderr, "[msr] hybrid multi-tile: %u tiles, quota %u / %u of depth %d, %u queries per chunk, %zu of %d "
-                             "queries repeated with quota = depth\n", n_tiles, quota_full, quota_last, depth, qc, redo.size(), nq);
+    if (debug_hybrid())
+        fprintf(stderr, "[msr] hybrid multi-tile: %u tiles, quota %u / %u of depth %d, %u queries per chunk, %zu of %d "
+                        "queries repeated with quota = depth\n", n_tiles, quota_full, quota_last, depth, qc, redo.size(), nq);
     if (rc == MSR_OK && !redo.empty()) {
         const uint32_t rows_cap = (uint32_t)std::min<size_t>(std::min<size_t>(cand_slots / (2 * per_tile_row * (size_t)depth), qc), redo.size());
         std::vector<uint16_t> qrows((size_t)rows_cap * dx->h);
@@ -2153,8 +1836,8 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
             for (uint32_t r = 0; r < rows; ++r)
                 memcpy(qrows.data() + (size_t)r * dx->h, q_fp16 + (size_t)redo[at + r] * dx->h, (size_t)dx->h * 2);
             // (d_Q's first rows are reused: the first round is over)
-            ok = hipMemsetAsync(d_Q, 0, (size_t)rows_pad * dx->h * 2, d->stream) == hipSuccess &&
-                 hipMemcpyAsync(d_Q, qrows.data(), (size_t)rows * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess &&
+            ok = hipMemsetAsync(s.d_Q, 0, (size_t)rows_pad * dx->h * 2, d->stream) == hipSuccess &&
+                 hipMemcpyAsync(s.d_Q, qrows.data(), (size_t)rows * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess &&
                  hipMemcpyAsync(d_qlist, redo.data() + at, (size_t)rows * 4, hipMemcpyHostToDevice, d->stream) == hipSuccess;
             if (!ok) {
                 set_error("upload failed in the second round of msr_hybrid_search");
@@ -2162,7 +1845,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
                 break;
             }
             hipEvent_t* e = ev.size() + 4 <= ev.capacity() ? four_events() : nullptr;
-            rc = launch_rows(d_Q, rows, 0, e);
+            rc = launch_rows(s.d_Q, rows, 0, e);
             if (rc == MSR_OK && hipStreamSynchronize(d->stream) != hipSuccess) {  // (qrows / redo are re-filled next)
                 set_error("hybrid kernels failed in the second round: %s", hipGetErrorString(hipGetLastError()));
                 rc = MSR_E_HIP;
@@ -2189,12 +1872,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
             t_cand += c;
             t_fuse += f;
         }
-        if (nq && (hipMemcpy(out_ord, d_ord, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(out_score, d_sf, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(out_n, d_n, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-            set_error("download failed in msr_hybrid_search");
-            rc = MSR_E_HIP;
-        }
+        rc = hybrid_download(ha, nq, k, out_ord, out_score, out_n);
     }
     if (ms) {
         ms[0] = t_cand;
@@ -2219,7 +1897,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
         else
             (void)hipEventDestroy(x);
     }
-    batch_free(b);
+    batch_free(s.b);
     return rc;
 }
 

@@ -1,7 +1,7 @@
 // Lab harness for the config-5 dense GEMM kernels: runs dense_scores_256w<NBUF, LAB> on random fp16 data at the bench shape,
 // checks a sample of the scores against a plain per-element dot product computed on the device in f32, and times it
 // with HIP events. Diagnostic only (scripts/gpu_gemm_lab.sh builds and runs it on the GPU box).
-#define MSR_GEMM_LAB 1
+#define MSR_LAB_GEMM 1
 #include "gemm_lab_kernels.hpp"
 
 #include <algorithm>

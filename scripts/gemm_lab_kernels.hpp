@@ -1,6 +1,7 @@
 // Experimental GEMM kernels of the hybrid path, kept for scripts/gemm_lab.hip (nothing in libmsr.so includes this file):
-// the steps between the 8-wave ping-pong kernel (csrc/msr_hybrid.hip: dense_scores_256p) and the production kernel
-// (csrc/msr_gemm_w4.hpp: dense_scores_256k). What each one measured is in DESIGN.md section 5.
+// the steps between the 8-wave ping-pong kernel dense_scores_256p (once in csrc/msr_hybrid.hip, now only in the git
+// history) and the production kernel (csrc/msr_gemm_w4.hpp: dense_scores_256k). What each one measured is in DESIGN.md
+// section 5.
 //
 // dense_scores_256w: the 256 x 256 block of Q . P^T on FOUR waves, one per SIMD, each 128 x 128 = 4 x 4 MFMA tiles of
 // 32 x 32 (v_mfma_f32_32x32x16_f16), software-pipelined inside the single wave instead of ping-pong between two.

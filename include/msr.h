@@ -128,9 +128,10 @@ int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, c
                    int32_t* out_n);
 
 /* Where the calling thread's last msr_search_csr spent its time, in microseconds: {query normalisation + device buffers
- * + upload enqueued, kernels enqueued, wait for the stream, download + copy out, release, the whole call, HIP-event span
- * of the scoring kernel(s), of the merge}. The reference calls batch_search with 4 queries at a time
- * (scripts/search_sparse.sh:16): such a call is launch- and copy-latency, not kernel time. */
+ * + upload enqueued, kernels enqueued, wait for the stream, download + copy out, release, the whole call, 0, 0}. Slots 6
+ * and 7 (once HIP-event spans of the kernels) stay in the ABI and are always 0: the call records no events. The reference
+ * calls batch_search with 4 queries at a time (scripts/search_sparse.sh:16): such a call is launch- and copy-latency,
+ * not kernel time. */
 int msr_search_laps(double out_us[8]);
 
 /* The same search for query STRINGS as the reference builds them (each token repeated `weight` times,
@@ -159,8 +160,8 @@ int msr_batch_kernel_ms(msr_batch* b, float* score_ms, float* merge_ms);
  * index's stream), so a whole timed region can be priced without a host sync per call. */
 int msr_batch_timing_reset(msr_batch* b);
 int msr_batch_timing_sum(msr_batch* b, int* n_calls, float* score_ms, float* merge_ms);
-/* Diagnostic builds only (env MSR_DEBUG_FLAGS bit 3): summed s_memtime deltas of wave 0 per kernel phase
- * {zero, stage, stream, wait, maxima, candidates, rank, -}. All zeros when the diagnostic is off. */
+/* Kept for ABI compatibility: the kernels' phase stamps were retired, so this writes eight zeros and returns MSR_OK
+ * (MSR_E_INVAL for a null batch or output). */
 int msr_batch_debug_stamps(msr_batch* b, unsigned long long out[8]);
 /* Algorithmic bytes of one search of this batch, SURVEY.md §8d:
  * sum over queries of  sum_t df(t)*(4+2) + |q|*12 + k*8  (df restricted to this handle's shard). */

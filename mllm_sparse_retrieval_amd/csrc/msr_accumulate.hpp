@@ -14,12 +14,12 @@
 
 namespace msr {
 
-// <docs per tile, threads, 1-KiB chunk loads per register bank, diagnostic build>; `lds` is the TileLds carve of the
-// calling kernel (accumulators first, then the staging / select union). Ends with a workgroup barrier: every
-// accumulator is final, the staging view of the union is dead.
-template <int TILE_DOCS, int NT, int U, bool DBG, class Stamp>
+// <docs per tile, threads, 1-KiB chunk loads per register bank>; `lds` is the TileLds carve of the calling kernel
+// (accumulators first, then the staging / select union). Ends with a workgroup barrier: every accumulator is final,
+// the staging view of the union is dead.
+template <int TILE_DOCS, int NT, int U>
 __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32_t q, const uint32_t tile_l,
-                                                const int rounds, uint8_t* const lds, SelectScratch& ss, Stamp stamp,
+                                                const int rounds, uint8_t* const lds, SelectScratch& ss,
                                                 const uint32_t tid) {
     constexpr int NW = NT / 64;
     static_assert(TILE_DOCS % (4 * NT) == 0, "tile must be a multiple of 4*NT");
@@ -74,7 +74,7 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
         constexpr int RG = 4;  // rounds per register group
         const uint32_t qv = lane < a.n_pairs ? a.q_dense[(uint64_t)q * a.n_pairs + lane] : 0u;
         // (the mask comes with the scalar load above, so the first rows are requested without waiting for qv)
-        const uint32_t pmask = (DBG && (a.dbg & 16u)) ? 0u : meta.z;
+        const uint32_t pmask = meta.z;
         const __amdgpu_buffer_rsrc_t rs_dense =
             make_rsrc(reinterpret_cast<const char*>(a.dense) + (uint64_t)tile_l * a.n_pairs * (TILE_DOCS * 4u),
                       a.n_pairs * (uint32_t)(TILE_DOCS * 4));
@@ -143,7 +143,6 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
         const uint32_t cnt = min((uint32_t)kQtBlock, qe - base);
         if (base != qb) __syncthreads();  // the previous round's readers of seg_* / pref are done (the accumulator
                                           // init is ordered before the atomics by the two barriers below)
-        stamp(0);  // zeroing (+ q_ptr fetch)
         // ---- stage the round's segments and an exclusive prefix sum of their chunk counts
         uint32_t nch = 0;
         if (tid < kQtBlock) {
@@ -177,8 +176,6 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
         // dense head terms and the one-chunk tail terms evenly. The (term, offset) of a wave's next 64 chunks is
         // resolved lane-parallel (one binary search per lane), then broadcast chunk by chunk with v_readlane, so
         // the inner loop is scalar control + one 16-byte load and four LDS atomics per lane.
-        stamp(1);  // staging: segment table + chunk-count scan
-        if (DBG && (a.dbg & 64u)) break;  // ablation: stop after staging
         const uint32_t total = rfl(pref[kQtBlock]);
         const uint32_t c_end = total > wave ? (total - wave + NW - 1) / NW : 0u;  // chunks of this wave
         for (uint32_t cb = 0; cb < c_end; cb += 64) {
@@ -198,8 +195,6 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
             const uint32_t m_b16 = my_i < c_end ? (seg_start[lo] + voff) << 4 : 0u;  // idle slots: the tile's first vec
             const uint32_t m_n16 = my_i < c_end ? min((uint32_t)kChunkVecs, seg_len[lo] - voff) << 4 : 0u;
             const uint32_t m_w = seg_w[lo];
-            stamp(7);  // lane-parallel chunk resolution (binary search)
-            if (DBG && (a.dbg & 256u)) break;  // ablation: stop after the first chunk resolution
             const uint32_t nchunk = min(64u, c_end - cb);
             // Software pipeline, two register banks of U chunks: the next bank's 1-KiB loads are in flight while
             // the current bank's LDS atomics issue. Loads are unconditional (lanes past a chunk's end, and chunk
@@ -213,17 +208,11 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
                     const uint32_t b16 = rdl(m_b16, idx);
                     const uint32_t n16 = rdl(m_n16, idx);
                     sn16[u] = n16;
-                    if (DBG && (a.dbg & 2u)) {  // ablation: no global loads, synthetic postings
-                        const uint32_t hsh = ((cb + idx) * 64u + lane) * 2654435761u;
-                        v[u] = make_uint4((1u << 16) | (hsh >> 17), (1u << 16) | ((hsh * 31u) >> 17),
-                                          (1u << 16) | ((hsh * 131u) >> 17), (1u << 16) | ((hsh * 1031u) >> 17));
-                    } else {
-                        // The chunk's END offset goes into the resource's size word: the buffer range check compares
-                        // scalar + lane offset with it, so lanes past the chunk's end — and every lane of an idle
-                        // slot — get zeros without a memory request, with no clamp instruction; the lane offset is
-                        // the loop-invariant lane16.
-                        v[u] = buf_load16(make_rsrc(post_base, b16 + n16), lane16, b16);
-                    }
+                    // The chunk's END offset goes into the resource's size word: the buffer range check compares
+                    // scalar + lane offset with it, so lanes past the chunk's end — and every lane of an idle slot —
+                    // get zeros without a memory request, with no clamp instruction; the lane offset is the
+                    // loop-invariant lane16.
+                    v[u] = buf_load16(make_rsrc(post_base, b16 + n16), lane16, b16);
                 }
             };
             auto add_bank = [&](const uint4 (&v)[U], const uint32_t (&sn16)[U], uint32_t u0) {
@@ -236,14 +225,8 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
                     // serialise); padding INSIDE a vec has weight 0 and a lane-distinct ordinal
                     if (lane16 < n16) {
                         const uint32_t p[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                        if (DBG && (a.dbg & 1u)) {  // ablation: no LDS atomics (keep the loads alive)
-                            if ((p[0] ^ p[1] ^ p[2] ^ p[3]) == 0xDEADBEEFu) atomicAdd(&acc[0], 1u);
-                        } else {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                atomicAdd(&acc[DBG ? (p[e] & 0xFFFFu) % TILE_DOCS : (p[e] & 0xFFFFu)],
-                                          __umul24(p[e] >> 16, w));
-                        }
+                        for (int e = 0; e < 4; ++e) atomicAdd(&acc[p[e] & 0xFFFFu], __umul24(p[e] >> 16, w));
                     }
                 }
             };
@@ -261,7 +244,6 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
             }
         }
     }
-    stamp(2);  // wave 0's own streaming
     __syncthreads();  // accumulation complete; the staging view of the union is dead from here on
 }
 
@@ -276,10 +258,10 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
 // a ballot + four v_readlane each, and has its first UL chunk loads IN FLIGHT before the accumulators are initialised,
 // so the posting latency hides behind the dense-head / zeroing phase. Two barriers in all (accumulators initialised;
 // accumulation complete).
-template <int TILE_DOCS, int NT, class Stamp>
+template <int TILE_DOCS, int NT>
 __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const uint32_t q, const uint32_t tile_l,
                                                       const int rounds, uint8_t* const lds, SelectScratch& ss,
-                                                      Stamp stamp, const uint32_t tid) {
+                                                      const uint32_t tid) {
     constexpr int NW = NT / 64;
     constexpr int UL = 4;  // chunk loads per wave and batch
     static_assert(TILE_DOCS % (4 * NT) == 0, "tile must be a multiple of 4*NT");
@@ -400,14 +382,12 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
         ss.tau0 = 1;
         ss.smax = 0;
     }
-    stamp(0);
     __syncthreads();  // every accumulator is initialised
     add_loaded();
     for (uint32_t u0 = UL; u0 < count_w; u0 += UL) {  // (rare on this path: more than UL chunks for one wave)
         resolve_and_load(u0);
         add_loaded();
     }
-    stamp(2);
     __syncthreads();  // accumulation complete
 }
 

@@ -27,17 +27,13 @@ static int launch_score(hipStream_t st, uint32_t tile_docs, uint32_t t_begin, ui
         switch (tile_docs) {
 #define MSR_LAUNCH(T, N, UU, W, WR)                                                                \
     if (dump)                                                                                      \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 512, false, 1>), grid, dim3(N), 0, st, a);   \
-    else if (a.dbg == 8u && a.k <= 512) /* stamps only: same shape as the production instance */  \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512, true>), grid, dim3(N), 0, st, a);        \
-    else if (a.dbg)                                                                                \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 1024, true>), grid, dim3(N), 0, st, a);      \
+        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 512, 1>), grid, dim3(N), 0, st, a);          \
     else if (a.k <= 512 && a.light && (T == 8192 || T == 4096))                                    \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512, false, 0, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a); \
+        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512, 0, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a); \
     else if (a.k <= 512)                                                                           \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512, false>), grid, dim3(N), 0, st, a);       \
+        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512>), grid, dim3(N), 0, st, a);              \
     else                                                                                           \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 1024, false>), grid, dim3(N), 0, st, a);     \
+        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 1024>), grid, dim3(N), 0, st, a);            \
     break;
             // <tile, threads, chunk loads per bank, min waves/SIMD of the k <= 512 instance, of the other instances>
             // LDS per workgroup = 4 B x tile + 4-8 KiB candidates + maxima -> workgroups (waves) per CU:
@@ -340,7 +336,7 @@ void batch_release_device(msr_batch* b) {
     (void)hipSetDevice(d->device);
     if (d->stream) (void)hipStreamSynchronize(d->stream);  // nothing in flight may still use the buffers
     // d_qptr .. d_n live inside pooled blocks; the rest are plain allocations
-    void** ptrs[] = {(void**)&b->d_gather, (void**)&b->d_stamps, (void**)&b->d_S, (void**)&b->d_R, (void**)&b->d_tpart};
+    void** ptrs[] = {(void**)&b->d_gather, (void**)&b->d_S, (void**)&b->d_R, (void**)&b->d_tpart};
     for (void** p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -695,8 +691,6 @@ void fill_score_args(ScoreArgs& sa, msr_batch* b, int k) {
     sa.unsorted = 0;
     sa.tpr = 1;
     sa.dump_add = 0;
-    sa.dbg = 0;
-    sa.stamps = nullptr;
     sa.light = 0;
 }
 
@@ -743,18 +737,6 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
     ScoreArgs sa;
     fill_score_args(sa, b, k);
     sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;
-    {
-        const char* dbg = getenv("MSR_DEBUG_FLAGS");
-        sa.dbg = dbg ? (uint32_t)strtoul(dbg, nullptr, 0) : 0u;
-        sa.stamps = nullptr;
-        if (sa.dbg & 8u) {
-            if (!b->d_stamps) {
-                HIP_TRY(hipMalloc(&b->d_stamps, 8 * sizeof(unsigned long long)));
-                HIP_TRY(hipMemsetAsync(b->d_stamps, 0, 8 * sizeof(unsigned long long), d->stream));
-            }
-            sa.stamps = b->d_stamps;
-        }
-    }
     // Staged search: the first `t1` tiles are scored with the full per-tile selection; their merged k-th best key
     // per query is a lower bound on the final k-th key, so the remaining tiles only have to report keys at or above
     // it (theta_select: one pass, usually no survivor). Exact: the final merge sees every key that can be in the
@@ -764,7 +746,7 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
     uint32_t t1 = nt;
     // (small launches — fewer (tile, query) pairs than one round of resident workgroups — stay in ONE launch: two
     // more kernels in the chain would cost the call more latency than the cheaper selection saves)
-    if (nt >= 2 && !sa.dbg && (uint64_t)nt * (uint64_t)b->nq >= kMinStagedPairs)
+    if (nt >= 2 && (uint64_t)nt * (uint64_t)b->nq >= kMinStagedPairs)
         t1 = std::max<uint32_t>(1u, nt / kStage1Fraction);
     sa.theta = nullptr;
     sa.unsorted = (b->unsorted_ok && nt == 1) ? 1u : 0u;  // one tile: its list IS the query's list
@@ -915,11 +897,7 @@ int msr_batch_debug_stamps(msr_batch* b, unsigned long long out[8]) {
         set_error("msr_batch_debug_stamps: bad argument");
         return MSR_E_INVAL;
     }
-    memset(out, 0, 8 * sizeof(unsigned long long));
-    if (!b->ix || !b->d_stamps) return MSR_OK;
-    int rc = msr_batch_sync(b);
-    if (rc != MSR_OK) return rc;
-    HIP_TRY(hipMemcpy(out, b->d_stamps, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    memset(out, 0, 8 * sizeof(unsigned long long));  // the phase stamps were retired: always zeros
     return MSR_OK;
 }
 
@@ -968,8 +946,7 @@ int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, c
     auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     const auto t0 = clk::now();
     msr_batch* b = nullptr;
-    static const bool timed_calls = getenv("MSR_TIME_SEARCH_CALLS") != nullptr;  // diagnostic: HIP events around the kernels
-    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, k, flags, 0, 0, &b, !timed_calls);
+    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, k, flags, 0, 0, &b, true);  // untimed: no HIP events
     if (rc != MSR_OK) return rc;
     const auto t1 = clk::now();
     rc = msr_batch_search(b, k);
@@ -978,19 +955,15 @@ int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, c
     const auto t3 = clk::now();
     if (rc == MSR_OK) rc = msr_batch_fetch(b, out_doc_ord, out_score, out_score_u32, out_n);
     const auto t4 = clk::now();
-    float score_ms = 0, merge_ms = 0;
-    if (rc == MSR_OK && b->timed) (void)msr_batch_kernel_ms(b, &score_ms, &merge_ms);
     msr_batch_destroy(b);
     const auto t5 = clk::now();
     g_laps[0] = us(t0, t1);  // query normalisation + pooled buffers + staging + upload enqueued
     g_laps[1] = us(t1, t2);  // kernels enqueued
     g_laps[2] = us(t2, t3);  // wait for the stream: upload + kernels (+ launch latency)
     g_laps[3] = us(t3, t4);  // download through pinned staging + copy out
-    g_laps[4] = us(t4, t5);  // events read, buffers back to the pool
+    g_laps[4] = us(t4, t5);  // buffers back to the pool
     g_laps[5] = us(t0, t5);  // the whole call
-    g_laps[6] = 1e3 * score_ms;  // HIP-event spans on the stream: scoring kernel(s) ...
-    g_laps[7] = 1e3 * merge_ms;  // ... and the merge
-    return rc;
+    return rc;  // (g_laps[6] and [7] stay 0: the call records no HIP events)
 }
 
 int msr_search_laps(double out_us[8]) {
@@ -1379,26 +1352,13 @@ static int termshard_emulated_impl(msr_index* const* hs, int n_shards, const int
             set_error("hipMalloc failed in msr_search_termshard_emulated");
             rc = MSR_E_NOMEM;
         }
-    // diagnostic (MSR_DEBUG_TERMSHARD): HIP-event time of every shard's dump and every logical rank's selection — the
-    // per-rank compute of the real protocol, which an 8-GPU run adds the reduce-scatter to (scripts/gpu_c4_termshard_probe.py)
-    static const bool dbg_ts = getenv("MSR_DEBUG_TERMSHARD") != nullptr;
-    std::vector<hipEvent_t> tev;
-    auto mark = [&]() {
-        if (!dbg_ts) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) == hipSuccess) (void)hipEventRecord(e, d->stream);
-        tev.push_back(e);
-    };
-    int n_passes = 0;
     for (uint32_t q0 = 0; q0 < (uint32_t)nq && rc == MSR_OK; q0 += p.qt) {
         const uint32_t qn = std::min<uint32_t>(p.qt, (uint32_t)nq - q0);
-        ++n_passes;
         if (hipMemsetAsync(d_S, 0, (size_t)qn * p.range_elems * p.G * 4, d->stream) != hipSuccess) {
             set_error("hipMemsetAsync failed");
             rc = MSR_E_HIP;
             break;
         }
-        mark();
         for (int g = 0; g < n_shards && rc == MSR_OK; ++g) {
             ScoreArgs sa;
             fill_score_args(sa, bs[g], k);
@@ -1408,7 +1368,6 @@ static int termshard_emulated_impl(msr_index* const* hs, int n_shards, const int
             sa.tpr = p.tpr;
             sa.dump_add = 1;
             rc = launch_score(d->stream, h->tile_docs, 0, h->n_tiles, sa, true);
-            mark();
         }
         for (int r = 0; r < n_shards && rc == MSR_OK; ++r) {
             SelectArgs se;
@@ -1424,29 +1383,8 @@ static int termshard_emulated_impl(msr_index* const* hs, int n_shards, const int
             se.qn = qn;
             se.k = (uint32_t)k;
             rc = launch_select(d->stream, h->tile_docs, se);
-            mark();
         }
     }
-    if (dbg_ts && rc == MSR_OK && hipStreamSynchronize(d->stream) == hipSuccess) {
-        // per pass: 1 + n_shards + n_shards marks
-        std::vector<double> dump_ms((size_t)n_shards, 0.0), sel_ms((size_t)n_shards, 0.0);
-        const size_t per = 1 + 2 * (size_t)n_shards;
-        for (int ps = 0; ps < n_passes; ++ps)
-            for (int i = 0; i < 2 * n_shards; ++i) {
-                hipEvent_t a = tev[(size_t)ps * per + (size_t)i], b2 = tev[(size_t)ps * per + (size_t)i + 1];
-                float ms = 0;
-                if (a && b2) (void)hipEventElapsedTime(&ms, a, b2);
-                (i < n_shards ? dump_ms[(size_t)i] : sel_ms[(size_t)(i - n_shards)]) += ms;
-            }
-        fprintf(stderr, "[msr] term shards G=%d, %d queries in %d passes of <= %u (send buffer %.2f GB per pass): dump ms per shard [",
-                n_shards, nq, n_passes, p.qt, (double)p.qt * (double)p.range_elems * p.G * 4 / 1e9);
-        for (int g = 0; g < n_shards; ++g) fprintf(stderr, "%s%.2f", g ? ", " : "", dump_ms[(size_t)g]);
-        fprintf(stderr, "] (on this one GPU a dump ADDS to the shared buffer: read + write), select ms per doc range [");
-        for (int r = 0; r < n_shards; ++r) fprintf(stderr, "%s%.2f", r ? ", " : "", sel_ms[(size_t)r]);
-        fprintf(stderr, "]\n");
-    }
-    for (hipEvent_t e : tev)
-        if (e) (void)hipEventDestroy(e);
     for (int r = 0; r < n_shards && rc == MSR_OK; ++r) {
         MergeArgs ma;
         ma.lists = rank_part[r];

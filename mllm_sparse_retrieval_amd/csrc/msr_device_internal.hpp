@@ -137,8 +137,6 @@ struct ScoreArgs {
     uint32_t tpr;              // tiles per rank = ceil(n_tiles / G)
     uint32_t dump_add;         // 1: dump[...] += tile (single-GPU emulation of the reduction), 0: store
     uint32_t light;            // 1: every query of the batch holds <= 64 sparse terms (score_tiles<..., LIGHT>)
-    uint32_t dbg;              // MSR_DEBUG_FLAGS (timing ablations only; results are wrong when bits 0-2 are set)
-    unsigned long long* stamps;  // [8] summed s_memtime deltas of wave 0 per phase (dbg bit 3), else null
 };
 
 struct SelectArgs {
@@ -194,7 +192,6 @@ struct msr_batch {
     uint32_t* d_su32 = nullptr;
     float* d_sf32 = nullptr;
     int32_t* d_n = nullptr;
-    unsigned long long* d_stamps = nullptr;  // diagnostic (MSR_DEBUG_FLAGS bit 3)
     // term-sharded search
     uint32_t* d_S = nullptr;      // [G][Qt][tpr*tile] partial accumulators of one query tile (reduce-scatter send buffer)
     uint32_t* d_R = nullptr;      // [Qt][tpr*tile] summed accumulators of this rank's doc range

@@ -3,7 +3,6 @@
 // (hybrid_tiles), the reference's min-max fusion for multi-tile indexes (fuse_tiles), the log1p-relu top-k sparsifier
 // (sparsify_keys), and their C-ABI entry points.
 // Selection and list merging reuse the search path's kernels (launch_select / launch_merge, msr_device.hip).
-#include <chrono>
 #include <cmath>
 
 #include "msr_accumulate.hpp"
@@ -574,7 +573,7 @@ __global__ __launch_bounds__(NT) void fuse_tiles(const FuseArgs a) {
     for (int i = tid; i < rounds * 4 * NT; i += NT) acc[i] = member[i] ? f32_to_key(facc[i]) : 0u;
     __syncthreads();
     tile_select<TILE_DOCS, NT, CAND>(reinterpret_cast<const uint4*>(lds), cand, tmax, wmax, ss, rounds, doc0, (int)a.k,
-                                     a.part + ((uint64_t)tile * a.nq + q) * a.k, [](int) {}, threadIdx.x);
+                                     a.part + ((uint64_t)tile * a.nq + q) * a.k, threadIdx.x);
 }
 
 }  // namespace msr
@@ -616,7 +615,6 @@ struct HybridArgs {
     uint32_t quota_full;      // candidates a full tile emits per side
     uint32_t quota_last;      // ... and the (shorter) last tile
     uint32_t* flags;          // [nq] hybrid_fuse_query: 1 = the candidate lists did not cover a depth list (second round)
-    unsigned long long* fq_stamps = nullptr;  // diagnostic (MSR_DEBUG_HYBRID): phase clocks of hybrid_fuse_query
 };
 
 // The rare paths of hybrid_tiles, kept OUT OF LINE: inlined, the general selections' live ranges cost the common path
@@ -650,7 +648,7 @@ template <int TILE_DOCS, int NT, int CAND>
 __device__ __attribute__((noinline)) void tile_select_general(const uint4* a4, uint64_t* cand, uint32_t* tmax, uint32_t* wmax,
                                                               SelectScratch* ss, int rounds, int k, uint64_t* out,
                                                               uint32_t tid) {
-    tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, *ss, rounds, 0ull, k, out, [](int) {}, tid);
+    tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, *ss, rounds, 0ull, k, out, tid);
 }
 
 // scratch of the dual selection (separate from the tile's LDS carve, which accumulate_tile and tile_select own)
@@ -668,7 +666,7 @@ struct DualScratch {
 //   (row, tile) candidate lists; hybrid_fuse_query (below) finishes the query. Exact by verification: the quota is the
 //   tile's expected share of a depth list plus five standard deviations; a query whose depth-th best lies below some
 //   tile's weakest candidate is flagged and repeated with quota = depth (every tile's own top-depth: always enough).
-template <int TILE_DOCS, int NT, int U, int MIN_WAVES, bool DBG = false, int MODE = 0>
+template <int TILE_DOCS, int NT, int U, int MIN_WAVES, int MODE = 0>
 __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a, const HybridArgs h) {
     constexpr int CAND = 1024;
     constexpr int E = TILE_DOCS / NT, R = E / 4, NW = NT / 64, HW = NW / 2;
@@ -692,16 +690,6 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63, wave = rfl(tid >> 6);
-    // diagnostic instance only (MSR_DEBUG_HYBRID): wave 0 of one workgroup in 64 adds its clock deltas per phase
-    long long t_prev = 0;
-    auto stamp = [&](int slot) {
-        if (DBG && a.stamps && tid == 0 && (blockIdx.x & 63u) == 0) {
-            const long long now = clock64();
-            if (slot >= 0) atomicAdd(&a.stamps[slot], (unsigned long long)(now - t_prev));
-            t_prev = now;
-        }
-    };
-    stamp(-1);
     const uint32_t q = (MODE == 1 && h.qlist) ? h.qlist[blockIdx.x] : a.q0 + blockIdx.x;
     const uint32_t tile_l = MODE == 1 ? blockIdx.y : 0u;  // (the hybrid paths take whole indexes: local tile = global tile)
     const uint64_t doc0 = (uint64_t)tile_l * TILE_DOCS;
@@ -711,8 +699,7 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
     if (tid < 8) ds.red[tid] = 0;  // (ordered before their first use by accumulate_tile's barriers)
     if (tid < 2) ds.ncand[tid] = 0;
     if (tid == 0) ds.fn = 0;
-    accumulate_tile<TILE_DOCS, NT, U, false>(a, q, tile_l, rounds, lds, ss, [](int) {}, tid);
-    stamp(0);
+    accumulate_tile<TILE_DOCS, NT, U>(a, q, tile_l, rounds, lds, ss, tid);
 
     // ---- the query's row of dense scores (the GEMM wrote the f32 values in ORDINAL order) in registers; docs past the
     // corpus become NaN: min / max skip them, every comparison with them is false
@@ -912,7 +899,6 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
     if (__builtin_expect(!fast_d, 0))
         T_d = threshold_general<TILE_DOCS, NT>(h.dkeys + (uint64_t)blockIdx.x * h.ld + doc0, rounds, ndocs, want, true, hist,
                                                cand + kHistBins / 2, &hs, tid);
-    stamp(1);
     if constexpr (MODE == 1) {
         // ---- the tile's candidates: every element at or above its side's threshold composite (exactly need_s / need_d
         // of them: composites are unique) becomes ONE record {ordinal, sparse score or 0, dense key or 0} — a doc that
@@ -966,7 +952,6 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
             m[0] = make_uint4((uint32_t)ws, (uint32_t)(ws >> 32), n_s, need_s == n_s ? 1u : 0u);
             m[1] = make_uint4((uint32_t)wd, (uint32_t)(wd >> 32), n_d, need_d == n_d ? 1u : 0u);
         }
-        stamp(2);
         return;
     }
     // ---- fusion (src/hybrid.py:32-53): min = the last member's score, max = the best, per side; fused keys go to the
@@ -1025,7 +1010,6 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
     n_mem = wave_sum_u32(n_mem);
     if (lane == 0) atomicAdd(&ds.red[5], n_mem);
     __syncthreads();
-    stamp(2);
     // ---- top-k of the fused scores: the bin of the k-th best, then every member at or above that bin is ranked
     const uint32_t n_members = ds.red[5];
     const uint32_t need_f = min(h.k, n_members);
@@ -1119,13 +1103,11 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
             }
             if (tid == 0) h.out_n[q] = (int32_t)need_f;
         }
-        stamp(3);
         return;
     }
     // ---- rare (many equal fused scores around the k-th place): the general tile selection over the fused keys
     tile_select_general<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, &ss, rounds, (int)h.k, res, tid);
     __syncthreads();
-    stamp(4);
     if (tid < h.k) {
         const uint64_t key = res[tid];
         const uint64_t o = (uint64_t)q * h.k + tid;
@@ -1267,14 +1249,6 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
     const uint32_t* const g_s = h.rec_s + (uint64_t)row * n_slots;
     const uint32_t* const g_d = h.rec_d + (uint64_t)row * n_slots;
     const uint4* const meta = h.tile_meta + (uint64_t)row * h.n_tiles * 2;
-    long long t_prev = h.fq_stamps ? clock64() : 0;
-    auto stamp = [&](int slot) {  // thread 0 of one workgroup in 16 adds its clock deltas per phase
-        if (h.fq_stamps && tid == 0 && (blockIdx.x & 15u) == 0) {
-            const long long now = clock64();
-            atomicAdd(&h.fq_stamps[slot], (unsigned long long)(now - t_prev));
-            t_prev = now;
-        }
-    };
     // Read in a loop from global memory, every pass below would pay a dependent L2 round trip per element (measured with
     // the first version of this kernel: 0.47 ms instead of 0.3 for 5 000 queries); queries with more records than the
     // registers hold (second round on many tiles) take that loop.
@@ -1319,11 +1293,8 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
     auto each_d = [&](auto f) { visit([&](uint32_t o, uint32_t, uint32_t dv) { f(comp(dv, o)); }); };
     uint32_t c_s, c_d;
     uint64_t mx_s, mx_d;
-    stamp(0);
     const uint64_t T_s = kth_largest_u64<NT>(each_s, need_s, ks, tid, &c_s, &mx_s);
-    stamp(1);
     const uint64_t T_d = kth_largest_u64<NT>(each_d, need_d, ks, tid, &c_d, &mx_d);
-    stamp(2);
     // ---- are the lists complete? a tile that did not emit everything it has must have its weakest candidate at or
     // below the side's depth-th best
     {
@@ -1343,7 +1314,6 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
         }
         return;
     }
-    stamp(3);
     // ---- fusion (src/hybrid.py:32-53; the dense term first: runs = [dense, sparse], src/search.py:459)
     const uint32_t self = h.self_ord ? (uint32_t)h.self_ord[q] : 0xFFFFFFFFu;
     const uint32_t smax_u = (uint32_t)(mx_s >> 32), smin_u = need_s ? (uint32_t)(T_s >> 32) : 0u;
@@ -1376,12 +1346,10 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
             for (uint32_t i = tid; i < n_slots; i += NT) f(fused_key(g_ord[i], g_s[i], g_d[i]));
         }
     };
-    stamp(4);
     // ---- top-k of the fused scores over the union (ties: lower ordinal)
     uint32_t members;
     uint64_t mx_f;
     const uint64_t T_f = kth_largest_u64<NT>(each_f, h.k, ks, tid, &members, &mx_f);
-    stamp(5);
     const uint32_t n_out = min(h.k, members);
     each_f([&](const uint64_t key) {
         if (key && key >= T_f) {
@@ -1402,7 +1370,6 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
         h.out_n[q] = (int32_t)n_out;
         h.flags[q] = 0;
     }
-    stamp(6);
 }
 
 // rows of the passage matrix in ORDINAL order: P_ord[row2ord[r]] = P[r]
@@ -1455,12 +1422,6 @@ static int ensure_ordinal_rows(msr_dense* dx, hipStream_t stream, const uint32_t
     return MSR_OK;
 }
 
-// diagnostic (MSR_DEBUG_HYBRID): phase clocks of the hybrid kernels, host laps, chunking and second-round counts
-static bool debug_hybrid() {
-    static const bool on = getenv("MSR_DEBUG_HYBRID") != nullptr;
-    return on;
-}
-
 // Score rows per chunk of queries of the two device-resident hybrid paths: the kernel after the GEMM reads its rows
 // back out of the Infinity Cache (80 to 1 024 MB measured within noise of each other)
 constexpr uint64_t kHybridChunkBytes = 160ull << 20;
@@ -1478,17 +1439,13 @@ struct HybridSetup {
 // The ordinal-ordered passage rows, the query batch (created for `batch_k`), the query matrix, `s_bytes` of score rows
 // and the result lists out of the handle's scratch, the uploads of the queries and of self_ord, and both argument
 // blocks. A non-zero return is an error before the batch exists; s.ok == false is a failed slot or upload (the caller
-// reports it and still owns s.b). `lap(what)` marks the host laps of the steps.
-template <class Lap>
+// reports it and still owns s.b).
 static int hybrid_setup(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
                         const uint16_t* q_fp16, int nq, int batch_k, int depth, int k, float alpha, uint32_t flags,
-                        const uint32_t* row2ord, const int32_t* self_ord, uint64_t ld, size_t s_bytes, Lap&& lap,
-                        HybridSetup& s) {
+                        const uint32_t* row2ord, const int32_t* self_ord, uint64_t ld, size_t s_bytes, HybridSetup& s) {
     DeviceIndex* d = ix->dev;
     if (int rc = ensure_ordinal_rows(dx, d->stream, row2ord, ix->host.h->n_docs)) return rc;
-    lap("ordinal map");
     if (int rc = msr_batch_create(ix, q_ptr, q_term, q_w, nq, batch_k, flags, &s.b)) return rc;
-    lap("sparse batch");
     const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
     const size_t perk = std::max<size_t>((size_t)nq * k, 1);
     s.d_Q = (_Float16*)dx->take(msr_dense::S_Q, std::max<size_t>((size_t)nq_pad * dx->h * 2, 16));
@@ -1542,18 +1499,6 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     const IndexHeader* h = ix->host.h;
     const uint64_t n = h->n_docs;
     HIP_TRY(hipSetDevice(d->device));
-    // diagnostic (MSR_DEBUG_HYBRID): host-side laps of the call, printed with the kernel span
-    auto t_last = std::chrono::steady_clock::now();
-    char laps[512];
-    size_t laps_n = 0;
-    laps[0] = 0;
-    auto lap = [&](const char* what) {
-        if (!debug_hybrid()) return;
-        const auto now = std::chrono::steady_clock::now();
-        const double msx = std::chrono::duration<double, std::milli>(now - t_last).count();
-        t_last = now;
-        if (laps_n < sizeof(laps)) laps_n += (size_t)snprintf(laps + laps_n, sizeof(laps) - laps_n, " %s %.2f", what, msx);
-    };
     const uint32_t nt_threads = h->tile_docs == 4096 ? 256u : 512u;
     const uint64_t ld = (n + 4 * nt_threads - 1) / (4 * nt_threads) * (4 * nt_threads);  // whole select rounds
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (n + 255) / 256 * 256);
@@ -1567,7 +1512,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * 256, std::max<uint32_t>(nq_pad, 256u));
     HybridSetup s;
     if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, k, depth, k, alpha, flags, row2ord, self_ord, ld,
-                               (size_t)qc * ld * 4, lap, s))
+                               (size_t)qc * ld * 4, s))
         return rc0;
     ScoreArgs& sa = s.sa;
     const HybridArgs& ha = s.ha;
@@ -1577,17 +1522,6 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
         rc = MSR_E_NOMEM;
     }
     std::vector<hipEvent_t> ev;
-    unsigned long long* d_stamps = nullptr;  // diagnostic (MSR_DEBUG_HYBRID): phase clocks of wave 0
-    if (debug_hybrid() && hipMalloc(&d_stamps, 8 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemsetAsync(d_stamps, 0, 8 * sizeof(unsigned long long), d->stream);
-    static const bool inner_events = getenv("MSR_HYBRID_NO_INNER_EVENTS") == nullptr;
-    lap("alloc + enqueue uploads");
-    hipEvent_t e_all[2] = {nullptr, nullptr};
-    if (rc == MSR_OK && (hipEventCreate(&e_all[0]) != hipSuccess || hipEventCreate(&e_all[1]) != hipSuccess)) {
-        set_error("hipEventCreate failed");
-        rc = MSR_E_HIP;
-    }
-    if (rc == MSR_OK) (void)hipEventRecord(e_all[0], d->stream);
     for (uint32_t q0 = 0; q0 < (uint32_t)nq && rc == MSR_OK; q0 += qc) {
         const uint32_t qn = std::min<uint32_t>(qc, (uint32_t)nq - q0);
         const uint32_t qn_pad = (qn + 255) / 256 * 256;
@@ -1600,17 +1534,14 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
             set_error("hipEventCreate failed");
             break;
         }
-        if (inner_events) (void)hipEventRecord(e[0], d->stream);
+        (void)hipEventRecord(e[0], d->stream);
         rc = launch_dense_gemm(dx, dx->d_P_ord, s.d_Q + (size_t)q0 * dx->h, s.d_S, qn, qn_pad, n_cover, ld, d->stream, true,
                                true);
         if (rc != MSR_OK) break;
-        if (inner_events) (void)hipEventRecord(e[1], d->stream);
+        (void)hipEventRecord(e[1], d->stream);
         sa.q0 = q0;
         sa.qn = qn;
-        sa.stamps = d_stamps;
-        if (d_stamps && h->tile_docs == 8192)
-            hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6, true>), dim3(qn), dim3(512), 0, d->stream, sa, ha);
-        else if (h->tile_docs == 4096)
+        if (h->tile_docs == 4096)
             hipLaunchKernelGGL((hybrid_tiles<4096, 256, 4, 5>), dim3(qn), dim3(256), 0, d->stream, sa, ha);
         else
             hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6>), dim3(qn), dim3(512), 0, d->stream, sa, ha);
@@ -1619,51 +1550,33 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
             rc = MSR_E_HIP;
             break;
         }
-        if (inner_events) (void)hipEventRecord(e[2], d->stream);
+        (void)hipEventRecord(e[2], d->stream);
     }
-    if (rc == MSR_OK) (void)hipEventRecord(e_all[1], d->stream);
     if (rc == MSR_OK && hipStreamSynchronize(d->stream) != hipSuccess) {
         set_error("hybrid kernels failed: %s", hipGetErrorString(hipGetLastError()));
         rc = MSR_E_HIP;
     }
-    float t_gemm = 0, t_fused = 0, t_all = 0;
-    if (rc == MSR_OK) (void)hipEventElapsedTime(&t_all, e_all[0], e_all[1]);
-    if (debug_hybrid()) fprintf(stderr, "[msr] hybrid pipeline span %.3f ms (inner events %d)\n", t_all, (int)inner_events);
-    lap("uploads + kernels");
+    float t_gemm = 0, t_fused = 0;
     if (rc == MSR_OK) {
-        // (only the per-chunk laps depend on the inner events; the results are downloaded either way)
-        for (size_t i = 0; inner_events && i + 2 < ev.size(); i += 3) {
+        for (size_t i = 0; i + 2 < ev.size(); i += 3) {
             float a = 0, c = 0;
             (void)hipEventElapsedTime(&a, ev[i], ev[i + 1]);
             (void)hipEventElapsedTime(&c, ev[i + 1], ev[i + 2]);
             t_gemm += a;
             t_fused += c;
         }
-        if (!inner_events) t_fused = t_all;  // the span is all there is: reported as the fused kernel's slot
         rc = hybrid_download(ha, nq, k, out_ord, out_score, out_n);
     }
-    lap("download");
     if (ms) {
         ms[0] = t_fused;
         ms[1] = t_gemm;
         ms[2] = 0.f;
         ms[3] = 0.f;
     }
-    if (d_stamps) {
-        unsigned long long st[8] = {0};
-        (void)hipMemcpy(st, d_stamps, sizeof(st), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[msr] hybrid_tiles wave-0 clocks: accumulate %llu, sparse select %llu, dense select %llu, fuse %llu, "
-                        "top-k %llu (sums over 1 workgroup in 64)\n", st[0], st[1], st[2], st[3], st[4]);
-        (void)hipFree(d_stamps);
-    }
     for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    for (hipEvent_t x : e_all)
         if (x) (void)hipEventDestroy(x);
     // (the scratch stays with the dense handle for the next call)
     batch_free(s.b);
-    lap("free");
-    if (debug_hybrid()) fprintf(stderr, "[msr] hybrid host laps (ms):%s\n", laps);
     return rc;
 }
 
@@ -1713,7 +1626,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     const size_t cand_slots = 2 * std::max<size_t>((size_t)qc * per_tile_row * quota_full, per_tile_row * (size_t)depth);
     HybridSetup s;  // (a batch for k = 1: only its query arrays are used)
     if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, 1, depth, k, alpha, flags, row2ord, self_ord, ld,
-                               (size_t)qc * ld * 4, [](const char*) {}, s))
+                               (size_t)qc * ld * 4, s))
         return rc0;
     ScoreArgs& sa = s.sa;
     HybridArgs& ha = s.ha;
@@ -1737,11 +1650,6 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     ha.quota_full = quota_full;
     ha.quota_last = quota_last;
     ha.flags = d_flags;
-    unsigned long long* d_fq = nullptr;
-    if (debug_hybrid() && hipMalloc(&d_fq, 16 * sizeof(unsigned long long)) == hipSuccess) {
-        (void)hipMemsetAsync(d_fq, 0, 16 * sizeof(unsigned long long), d->stream);
-        ha.fq_stamps = d_fq;
-    }
     // one pass of the three kernels over `rows` launch rows (queries q0 .. or the listed ones), dense rows from d_Qrows
     auto launch_rows = [&](const _Float16* d_Qrows, uint32_t rows, uint32_t q0, hipEvent_t* e) -> int {
         const uint32_t rows_pad = (rows + 255) / 256 * 256;
@@ -1757,13 +1665,10 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
                 return MSR_E_RANGE;
             }
             const dim3 grid(rows, n_tiles);
-            sa.stamps = reinterpret_cast<unsigned long long*>(ha.fq_stamps ? ha.fq_stamps + 8 : nullptr);
             if (tile == 4096)
-                hipLaunchKernelGGL((hybrid_tiles<4096, 256, 4, 5, false, 1>), grid, dim3(256), 0, d->stream, sa, ha);
-            else if (sa.stamps)  // diagnostic (MSR_DEBUG_HYBRID): wave 0 of one workgroup in 64 adds its phase clocks
-                hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6, true, 1>), grid, dim3(512), 0, d->stream, sa, ha);
+                hipLaunchKernelGGL((hybrid_tiles<4096, 256, 4, 5, 1>), grid, dim3(256), 0, d->stream, sa, ha);
             else
-                hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6, false, 1>), grid, dim3(512), 0, d->stream, sa, ha);
+                hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6, 1>), grid, dim3(512), 0, d->stream, sa, ha);
         }
         if (hipGetLastError() != hipSuccess) {
             set_error("hybrid_tiles launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1821,9 +1726,6 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     std::vector<uint32_t> redo;
     for (int i = 0; i < nq && rc == MSR_OK; ++i)
         if (hflags[(size_t)i]) redo.push_back((uint32_t)i);
-    if (debug_hybrid())
-        fprintf(stderr, "[msr] hybrid multi-tile: %u tiles, quota %u / %u of depth %d, %u queries per chunk, %zu of %d "
-                        "queries repeated with quota = depth\n", n_tiles, quota_full, quota_last, depth, qc, redo.size(), nq);
     if (rc == MSR_OK && !redo.empty()) {
         const uint32_t rows_cap = (uint32_t)std::min<size_t>(std::min<size_t>(cand_slots / (2 * per_tile_row * (size_t)depth), qc), redo.size());
         std::vector<uint16_t> qrows((size_t)rows_cap * dx->h);
@@ -1879,16 +1781,6 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
         ms[1] = t_gemm;
         ms[2] = 0.f;
         ms[3] = t_fuse;
-    }
-    if (d_fq) {
-        unsigned long long st[16] = {0};
-        (void)hipMemcpy(st, d_fq, sizeof(st), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[msr] hybrid_tiles<MODE 1> wave-0 clocks (1 workgroup in 64): accumulate + dense row %llu, dual quota "
-                        "selection %llu, emission %llu\n", st[8], st[9], st[10]);
-        fprintf(stderr, "[msr] hybrid_fuse_query thread-0 clocks (1 workgroup in 16): load+init %llu, sparse depth-th %llu, dense "
-                        "depth-th %llu, verify %llu, fusion %llu, fused k-th %llu, collect+rank+store %llu\n",
-                st[0], st[1], st[2], st[3], st[4], st[5], st[6]);
-        (void)hipFree(d_fq);
     }
     for (hipEvent_t x : ev) {
         if (!x) continue;

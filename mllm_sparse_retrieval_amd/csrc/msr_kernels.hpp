@@ -2,7 +2,7 @@
 // §8d); no MFMA — this is gather + integer reduce, and what it actually runs into is VALU issue and the L2 -> CU path
 // (DESIGN.md §7).
 //
-// score_tiles<TILE_DOCS, NT, U, MIN_WAVES, CAND, DBG, MODE>   one workgroup per (doc tile, query); grid = (query, tile)
+// score_tiles<TILE_DOCS, NT, U, MIN_WAVES, CAND, MODE, LIGHT>   one workgroup per (doc tile, query); grid = (query, tile)
 //     - TILE_DOCS u32 accumulators in LDS (32 KiB at the default 8192 docs: four workgroups = 32 waves per CU),
 //     - dense-head terms: doc-major rows scored by the accumulator's owner with v_dot2_u32_u16 (this is also the
 //       accumulator init),
@@ -60,9 +60,10 @@ __device__ __forceinline__ void merge_wave(const MergeArgs& a, const uint32_t q,
 }
 
 // ------------------------------------------------------------------------------------------------ kernel 1
-// <docs per tile, threads, 1-KiB chunk loads per register bank, min waves per SIMD, candidate-key capacity (>= k), diag>
+// <docs per tile, threads, 1-KiB chunk loads per register bank, min waves per SIMD, candidate-key capacity (>= k)>
+// MODE 1: term-sharded search (dump the accumulator tile instead of selecting)
 // LIGHT: the batch's queries hold at most 64 sparse terms each -> accumulate_tile_light (msr_accumulate.hpp)
-template <int TILE_DOCS, int NT, int U, int MIN_WAVES, int CAND, bool DBG, int MODE = 0, bool LIGHT = false>
+template <int TILE_DOCS, int NT, int U, int MIN_WAVES, int CAND, int MODE = 0, bool LIGHT = false>
 __global__ __launch_bounds__(NT, MIN_WAVES) void score_tiles(const ScoreArgs a) {
     using L = TileLds<TILE_DOCS, NT, CAND>;
 
@@ -76,17 +77,6 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void score_tiles(const ScoreArgs a) 
     SelectScratch& ss = *reinterpret_cast<SelectScratch*>(un + L::kUnion + L::kTmax);
 
     const uint32_t tid = threadIdx.x;
-    // diagnostic build only: wave 0 stamps s_memtime at phase boundaries and adds the deltas to a side buffer
-    long long t_prev = 0;
-    auto stamp = [&](int slot) {
-        if (DBG && (a.dbg & 8u) && a.stamps && tid == 0 && (blockIdx.x & 63u) == 0) {  // 1 workgroup in 64
-            const long long now = clock64();
-            if (slot >= 0) atomicAdd(&a.stamps[slot], (unsigned long long)(now - t_prev));
-            t_prev = now;
-        }
-    };
-    stamp(-1);
-    if (DBG && (a.dbg & 128u)) return;  // ablation: workgroup launch cost only
     // 2-D grid (x = query, y = tile): x runs fastest in dispatch order, so neighbours share the tile (tile-major)
     // without a division in every wave's prologue
     const uint32_t tile_l = a.tl0 + blockIdx.y;
@@ -101,10 +91,9 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void score_tiles(const ScoreArgs a) 
     // staged search: the query's k-th best key over the tiles of an earlier launch (0: fewer than k hits so far)
     const uint64_t theta = (MODE == 0 && a.theta) ? a.theta[(uint64_t)q * a.k + (a.k - 1)] : 0ull;
     if constexpr (LIGHT)
-        accumulate_tile_light<TILE_DOCS, NT>(a, q, tile_l, rounds, lds, ss, stamp, tid);
+        accumulate_tile_light<TILE_DOCS, NT>(a, q, tile_l, rounds, lds, ss, tid);
     else
-        accumulate_tile<TILE_DOCS, NT, U, DBG>(a, q, tile_l, rounds, lds, ss, stamp, tid);
-    stamp(3);  // waiting for the slowest wave
+        accumulate_tile<TILE_DOCS, NT, U>(a, q, tile_l, rounds, lds, ss, tid);
 
     // =============================================================== exact top-k of this tile
     // Thread `tid` owns vec r*NT + tid of the accumulators in round r (conflict-free ds_read_b128); the
@@ -124,18 +113,9 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void score_tiles(const ScoreArgs a) 
     }
     uint64_t* out = a.part + ((uint64_t)tile_l * a.nq + q) * a.k;
     const int k = (int)a.k;
-    if (DBG && (a.dbg & 4u)) {  // ablation: no select phase
-        for (int i = tid; i < k; i += NT) out[i] = 0;
-        return;
-    }
 
-    if (theta && theta_select<TILE_DOCS, NT, CAND>(a4, cand, ss, rounds, doc0, k, out, theta, tid)) {
-        stamp(6);
-        return;
-    }
-    tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, ss, rounds, doc0, k, out, stamp, tid,
-                                     a.unsorted != 0);
-    stamp(6);  // ranking + output
+    if (theta && theta_select<TILE_DOCS, NT, CAND>(a4, cand, ss, rounds, doc0, k, out, theta, tid)) return;
+    tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, ss, rounds, doc0, k, out, tid, a.unsorted != 0);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel 1b
@@ -173,8 +153,7 @@ __global__ __launch_bounds__(NT) void select_tiles(const SelectArgs a) {
         ss.smax = 0;
     }
     __syncthreads();
-    tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, ss, rounds, doc0, (int)a.k, out, [](int) {}, tid,
-                                     a.unsorted != 0);
+    tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, ss, rounds, doc0, (int)a.k, out, tid, a.unsorted != 0);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel 2

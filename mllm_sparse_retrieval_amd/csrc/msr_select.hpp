@@ -173,10 +173,10 @@ namespace msr {
 // Thread `tid` owns vec r*NT + tid of the accumulators in round r (conflict-free ds_read_b128); the accumulators are
 // re-read from LDS in every pass instead of being held in registers. Writes k keys best-first (0 = empty slot).
 // `unsorted`: the k keys may be written in any order (see the end of the function).
-template <int TILE_DOCS, int NT, int CAND, class Stamp>
+template <int TILE_DOCS, int NT, int CAND>
 __device__ __forceinline__ void tile_select(const uint4* a4, uint64_t* cand, uint32_t* tmax, uint32_t* wmax,
                                             SelectScratch& ss, int rounds, uint64_t doc0, int k,
-                                            uint64_t* __restrict__ out, Stamp stamp, const uint32_t tid,
+                                            uint64_t* __restrict__ out, const uint32_t tid,
                                             const bool unsorted = false) {
     constexpr int NW = NT / 64;
     const uint32_t lane = tid & 63;
@@ -239,7 +239,6 @@ __device__ __forceinline__ void tile_select(const uint4* a4, uint64_t* cand, uin
         }
     }
 
-    stamp(4);  // thread / wave maxima, tau0
     // ---- candidates: accumulators >= tau0 as unique global keys (score << 32 | ~ordinal)
     if (mymax >= tau0) {
         for (int r = 0; r < rounds; ++r) {
@@ -256,7 +255,6 @@ __device__ __forceinline__ void tile_select(const uint4* a4, uint64_t* cand, uin
         }
     }
     __syncthreads();
-    stamp(5);  // candidate collection
     uint32_t n_cand = ss.n_cand;
 
     if (TILE_DOCS <= 8192 && CAND >= 2 * kHistCand && n_cand > CAND) {

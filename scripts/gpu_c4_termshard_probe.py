@@ -1,16 +1,16 @@
 """Per-rank compute of the TERM-range sharded config-4 search (BASELINE.json configs[3]), measured on ONE GPU: for G in
 2, 4, 8 the G term-shard handles (msr_index_open_termshard: the postings a rank of a G-GPU run would hold) play the exact
 protocol in turn — every shard dumps its partial accumulator tiles (score_tiles<MODE 1>), the sums of every doc range
-are selected (select_tiles, 16 tiles per range at G = 8), the range lists are merged — and libmsr prints the HIP-event
-time of every shard's dump and every range's selection (MSR_DEBUG_TERMSHARD). What cannot run here is the exchange
-itself: ncclReduceScatter of nq x N x 4 B = 40 GB per step; its volume is printed next to the compute so that DESIGN.md §6
-can price the 8-GPU step as compute + bytes / xGMI rate. usage: python scripts/gpu_c4_termshard_probe.py [n_queries]"""
+are selected (select_tiles, 16 tiles per range at G = 8), the range lists are merged. Per G it prints the resident
+bytes per shard, the host wall time of the whole emulation and whether its result is identical to the unsharded one.
+What cannot run here is the exchange itself: ncclReduceScatter of nq x N x 4 B = 40 GB per step; its volume is printed
+next to the compute so that DESIGN.md §6 can price the 8-GPU step as compute + bytes / xGMI rate.
+usage: python scripts/gpu_c4_termshard_probe.py [n_queries]"""
 import os
 import sys
 import tempfile
 import time
 
-os.environ["MSR_DEBUG_TERMSHARD"] = "1"
 import numpy as np  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

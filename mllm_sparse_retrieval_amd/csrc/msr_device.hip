@@ -955,6 +955,9 @@ int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, c
     const auto t3 = clk::now();
     if (rc == MSR_OK) rc = msr_batch_fetch(b, out_doc_ord, out_score, out_score_u32, out_n);
     const auto t4 = clk::now();
+    // a failed search may have enqueued kernels that still read and write the handle's mapped block, which the next
+    // small call reuses: let them finish first
+    if (rc != MSR_OK && b->zero_copy) (void)hipStreamSynchronize(ix->dev->stream);
     msr_batch_destroy(b);
     const auto t5 = clk::now();
     g_laps[0] = us(t0, t1);  // query normalisation + pooled buffers + staging + upload enqueued

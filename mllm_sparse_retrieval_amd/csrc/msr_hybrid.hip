@@ -1956,8 +1956,8 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
 namespace msr {
 
 __global__ __launch_bounds__(256) void sparsify_keys(const void* __restrict__ logits, int is_f16, int fp16_math,
-                                                     uint32_t* __restrict__ out, uint32_t V, uint64_t ld) {
-    const uint32_t row = blockIdx.y;
+                                                     uint32_t* __restrict__ out, uint32_t V, uint64_t ld, uint32_t row0) {
+    const uint32_t row = row0 + blockIdx.y;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < V; i += gridDim.x * 256) {
         float x = is_f16 ? (float)reinterpret_cast<const _Float16*>(logits)[(uint64_t)row * V + i]
                          : reinterpret_cast<const float*>(logits)[(uint64_t)row * V + i];
@@ -1982,6 +1982,10 @@ extern "C" int msr_sparsify(const void* logits, int is_f16, int fp16_math, int r
     }
     if (k < 1 || k > MSR_KMAX) {
         set_error("k must be in [1, %d] (got %d)", MSR_KMAX, k);
+        return MSR_E_RANGE;
+    }
+    if ((uint32_t)k > vocab) {  // torch.topk refuses k > vocab too; the selection would pad with id 0xFFFFFFFF
+        set_error("k=%d exceeds the vocabulary of %u", k, vocab);
         return MSR_E_RANGE;
     }
     int n_dev = 0;
@@ -2014,8 +2018,10 @@ extern "C" int msr_sparsify(const void* logits, int is_f16, int fp16_math, int r
         rc = MSR_E_NOMEM;
     }
     if (rc == MSR_OK) {
-        hipLaunchKernelGGL(sparsify_keys, dim3(std::min<uint32_t>((vocab + 255) / 256, 1024), (uint32_t)rows), dim3(256), 0, st,
-                           d_in, is_f16, fp16_math, d_keys, vocab, ld);
+        for (uint32_t r0 = 0; r0 < (uint32_t)rows; r0 += kMaxGridY)  // rows in slices of the grid's y limit
+            hipLaunchKernelGGL(sparsify_keys,
+                               dim3(std::min<uint32_t>((vocab + 255) / 256, 1024), std::min<uint32_t>(kMaxGridY, (uint32_t)rows - r0)),
+                               dim3(256), 0, st, d_in, is_f16, fp16_math, d_keys, vocab, ld, r0);
         SelectArgs se;
         se.unsorted = 0;
         se.src = d_keys;

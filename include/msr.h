@@ -236,7 +236,8 @@ int msr_dense_search(msr_dense* dx, const uint16_t* q_fp16, int nq, int k, uint3
  * bit for bit (v_mfma_f32_32x32x2_f32, one accumulator per score, no split-K, subnormals kept), so a score does not
  * depend on the batch it was searched in. Outputs, key map, padding and tie rule (lower ROW wins) are those of
  * msr_dense_search; 1 <= k <= MSR_KMAX. A handle holds one precision: msr_dense_search on an f32 handle,
- * msr_dense_search_f32 on an fp16 handle and msr_hybrid_search with an f32 handle fail with MSR_E_INVAL.
+ * msr_dense_search_f32 on an fp16 handle, msr_hybrid_search with an f32 handle and msr_hybrid_search_f32 with an fp16
+ * handle fail with MSR_E_INVAL.
  * msr_dense_close and msr_dense_stats serve both kinds. */
 int msr_dense_open_f32(const float* p, uint64_t n, uint32_t h, int device, msr_dense** out);
 int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
@@ -275,6 +276,17 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
                       const uint16_t* q_fp16, int nq, int depth, int k, float alpha, uint32_t flags,
                       const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n,
                       float ms[4]);
+/* ---- f32 hybrid search: msr_hybrid_search with the dense side of the reference's default run (an f32 IndexFlatIP,
+ * no --use_gpu: src/arguments.py:63, src/search.py:232-237,254-270). The contract is msr_hybrid_search's — the same three
+ * paths chosen by the same rules, the same ms layout, the same dense tie rule per path — except that:
+ *   - dx comes from msr_dense_open_f32 (an fp16 handle: MSR_E_INVAL; an f32 handle given to msr_hybrid_search: likewise);
+ *   - q is [nq][h] row-major f32, any h >= 1;
+ *   - every dense score is the k-ordered fmaf chain of msr_dense_search_f32, so it has the same bits as that call on the
+ *     same rows (the two fused paths run the same f32 GEMM on the ordinal-ordered rows, a second n_pad x hp x 4-byte
+ *     copy on the device, built once per mapping and freed by msr_dense_close). */
+int msr_hybrid_search_f32(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                          const float* q, int nq, int depth, int k, float alpha, uint32_t flags, const uint32_t* row2ord,
+                          const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n, float ms[4]);
 
 /* ---- encode-side sparsifier: log(1 + relu(logit)) -> top-k -> rint(x * 100) (src/model.py:104, src/encode.py:69-75).
  * logits: row-major [rows][vocab], f32 (is_f16 = 0) or IEEE fp16 (is_f16 = 1). fp16_math = 1 rounds 1 + relu and the

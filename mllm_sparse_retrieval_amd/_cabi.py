@@ -94,6 +94,7 @@ SYMBOLS = [
     ("msr_dense_stats", _I, [_VP, _VP]),
     ("msr_f32_to_f16", _I, [_VP, _VP, _U64, _I]),
     ("msr_hybrid_search", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("msr_hybrid_search_f32", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_sparsify", _I, [_VP, _I, _I, _I, _U32, _I, _I, _VP, _VP, _VP]),
     ("msr_synth_vectors", _I, [_U64, _U32, _U32, C.c_double, _U64, _I, _VP, _VP, _VP]),
     ("msr_last_error", _CP, []),

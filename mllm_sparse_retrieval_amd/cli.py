@@ -122,6 +122,12 @@ def _check_search_args(a):
         sys.exit("search: give --sparse_index (sparse or hybrid search) and/or --passage_reps (dense search)")
     if a.sparse_index is None and not 1 <= a.depth <= MSR_KMAX:
         sys.exit(f"search: dense-only --depth must be in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth})")
+    if getattr(a, "hybrid_f32", False):
+        if a.use_gpu:
+            sys.exit("search: --hybrid_f32 and --use_gpu contradict each other (--use_gpu is the reference's fp16 GPU "
+                     "index, --hybrid_f32 its f32 CPU index)")
+        if a.sparse_index is None or a.passage_reps is None:
+            sys.exit("search: --hybrid_f32 applies to hybrid search: give both --passage_reps and --sparse_index")
 
 
 def _cmd_search(a):
@@ -198,7 +204,7 @@ def _cmd_search(a):
         if p_reps is not None:  # --host_fusion: the reference's own structure, batch by batch (src/search.py:455-461)
             from .dense import FaissFlatSearcher
 
-            dense_retriever = FaissFlatSearcher(p_reps, device=a.device)
+            dense_retriever = FaissFlatSearcher(p_reps, device=a.device, precision="f32" if getattr(a, "hybrid_f32", False) else "fp16")
             dense_retriever.add(p_reps)
         for i in range(0, len(qids), bs):
             scores, rankings = sparse_search(searcher, texts[i:i + bs], qids[i:i + bs], args)
@@ -284,12 +290,13 @@ def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
     """search --passage_reps on the GPU: ONE msr_hybrid_search call for the fused run; the sparse and the dense run the
     reference also reports (src/metrices.py:105-126) come from one whole-shard call each. Returns the three run dicts in
     the reference's layouts (src/search.py:66-82; the fused run without the 'docs' level, src/hybrid.py:32-53).
+    --hybrid_f32: an f32 DenseIndex and hybrid_search_f32 (the reference's f32 flat index) instead of fp16.
     Difference to --host_fusion: the fused run holds the best --fusion_k docs of the union (the recall reporter reads
     200, src/metrices.py:9), and an exact tie of two DENSE scores at the depth boundary goes to the lower doc ordinal
     instead of the lower row (include/msr.h)."""
     import numpy as np
 
-    from .dense import DenseIndex, hybrid_search, row_to_ordinal
+    from .dense import DenseIndex, hybrid_search, hybrid_search_f32, row_to_ordinal
     from .run import get_run_dict
 
     ix = searcher.index
@@ -298,14 +305,16 @@ def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
     q_ptr, q_term, q_w = ix.encode_queries(texts)
     q = np.stack([q_reps_by_id[x] for x in qids]).astype(np.float32) if qids else np.zeros((0, p_reps.shape[1]), np.float32)
     q = q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), 1e-12)                # F.normalize, src/search.py:342
-    dix = DenseIndex(p_reps, device=ix.device)
+    f32 = bool(getattr(a, "hybrid_f32", False))
+    dix = DenseIndex(p_reps, device=ix.device, precision="f32" if f32 else "fp16")
+    hybrid = hybrid_search_f32 if f32 else hybrid_search
     try:
         table = ix.docid_table()
         ord_of = {d: o for o, d in enumerate(table.tolist())}
         r2o = np.asarray([ord_of[str(x)] for x in p_lookup], dtype=np.uint32)
         self_ord = np.asarray([ord_of.get(x, -1) for x in qids], dtype=np.int32) if a.remove_query else None
         drop = searcher.min_idf >= 0 if searcher.drop_df_eq_n is None else bool(searcher.drop_df_eq_n)
-        ords, fs, cnt, _ = hybrid_search(ix, dix, q_ptr, q_term, q_w, q, depth, k_f, a.alpha, r2o, self_ord, drop_df_eq_n=drop)
+        ords, fs, cnt, _ = hybrid(ix, dix, q_ptr, q_term, q_w, q, depth, k_f, a.alpha, r2o, self_ord, drop_df_eq_n=drop)
         fs_rows = fs.tolist()
         fusion_run = {qid: dict(zip(table[ords[i, :cnt[i]]].tolist(), fs_rows[i][:cnt[i]])) for i, qid in enumerate(qids)}
         sparse_run, dense_run = {}, {}
@@ -401,13 +410,17 @@ def main(argv=None):
     s.add_argument("--quiet", action="store_true")
     s.add_argument("--use_gpu", action="store_true",
                    help="dense-only search: fp16 passage storage like the reference's faiss GPU clone (default f32, "
-                        "its CPU index); ignored by the sparse and hybrid routes")
+                        "its CPU index); ignored by the sparse and hybrid routes (hybrid precision: --hybrid_f32)")
     s.add_argument("--queries", default=None)
     s.add_argument("--qrels", default=None)
     s.add_argument("--device", type=int, default=0)
     s.add_argument("--host_fusion", action="store_true",
                    help="hybrid: the reference's own structure (dense + sparse lists per batch, fuse() on the host) "
                         "instead of one msr_hybrid_search call over the whole query file")
+    s.add_argument("--hybrid_f32", action="store_true",
+                   help="hybrid: f32 dense side (the reference's default f32 flat index, no --use_gpu) on both the GPU "
+                        "route (msr_hybrid_search_f32) and --host_fusion, instead of fp16 storage; needs --passage_reps "
+                        "and --sparse_index, refused with --use_gpu")
     s.add_argument("--fusion_k", type=int, default=1000, help="hybrid on the GPU: docs kept of each query's fused union (<= 1024)")
     s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs")
     s.add_argument("--compat-denominator", "--compat_denominator", dest="compat_denominator", action="store_true",

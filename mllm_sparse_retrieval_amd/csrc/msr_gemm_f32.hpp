@@ -31,6 +31,8 @@ constexpr int kF32TileB = 128 * kF32RowB;     // one operand stage (128 rows)
 // the next step's global loads (2 x 16 B per operand per thread) are in flight while the current step's 32 MFMAs run.
 // Q has a multiple of 128 rows and P at least d_blk + 128 readable rows (both zero padded); H % kF32KStep == 0.
 // Rows q >= M are not written; columns d >= N get key 0 (padding that select_tiles reads as "no doc").
+// RAW = 1 (the hybrid paths): the f32 bit patterns of the scores are written as they are, padding columns still 0.
+template <int RAW>
 __global__ __launch_bounds__(256) void dense_scores_f32(const float* __restrict__ Q, const float* __restrict__ P,
                                                         uint32_t* __restrict__ out, uint32_t M, uint32_t N, uint32_t H,
                                                         uint64_t ld) {
@@ -112,7 +114,8 @@ __global__ __launch_bounds__(256) void dense_scores_f32(const float* __restrict_
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const uint32_t q = q_blk + wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (q < M) out[(uint64_t)q * ld + d] = d < N ? f32_to_key(acc[i][j][e]) : 0u;
+                if (q < M)
+                    out[(uint64_t)q * ld + d] = d < N ? (RAW ? __float_as_uint(acc[i][j][e]) : f32_to_key(acc[i][j][e])) : 0u;
             }
         }
 }

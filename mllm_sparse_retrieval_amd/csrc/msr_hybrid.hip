@@ -124,9 +124,9 @@ struct msr_dense {
     uint32_t h = 0;
     uint32_t tile_docs = 0;
     uint32_t n_tiles = 0;
-    // hybrid path on single-tile indexes: the same rows in doc-ORDINAL order (P_ord[row2ord[r]] = P[r]), built on first
-    // use and kept while the mapping stays the same
-    _Float16* d_P_ord = nullptr;
+    // hybrid paths: the same rows in doc-ORDINAL order (P_ord[row2ord[r]] = P[r]), in the handle's precision and row
+    // layout ([n_pad][h] fp16 or [n_pad][hp] f32), built on first use and kept while the mapping stays the same
+    void* d_P_ord = nullptr;
     std::vector<uint32_t> ord_map;
     bool lds_attr_set = false;  // dense_scores_256k needs the 128 KiB dynamic-LDS opt-in once per device
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
@@ -283,15 +283,21 @@ static int launch_dense_gemm(msr_dense* dx, const _Float16* P, const _Float16* d
     return MSR_OK;
 }
 
-// The f32 GEMM of an f32 handle: keys of C = Q * P^T into out[q][ld] for doc columns [0, n_cover); Q rows padded to qn_pad
-// (a multiple of 128) and K to dx->hp in the device copy. Doc blocks in slices of at most 65535 (grid y limit).
-static int launch_dense_gemm_f32(msr_dense* dx, const float* d_Q, uint32_t* d_S, uint32_t qn, uint32_t qn_pad,
-                                 uint64_t n_cover, uint64_t ld, hipStream_t st) {
+// The f32 GEMM of an f32 handle: keys (raw: f32 bit patterns) of C = Q * P^T into out[q][ld] for doc columns
+// [0, n_cover); P is [>= n_cover][dx->hp] (d_P32 or the ordinal-ordered copy), Q rows padded to qn_pad (a multiple of
+// 128) and K to dx->hp in the device copy. Doc blocks in slices of at most 65535 (grid y limit).
+static int launch_dense_gemm_f32(msr_dense* dx, const float* P, const float* d_Q, uint32_t* d_S, uint32_t qn,
+                                 uint32_t qn_pad, uint64_t n_cover, uint64_t ld, hipStream_t st, bool raw = false) {
     for (uint64_t d0 = 0; d0 < n_cover; d0 += 128ull * kMaxGridY) {
         const uint64_t nd = std::min<uint64_t>(n_cover - d0, 128ull * kMaxGridY);
         const uint32_t n_left = dx->n > d0 ? (uint32_t)std::min<uint64_t>(dx->n - d0, 0xFFFFFFFFull) : 0u;
-        hipLaunchKernelGGL(dense_scores_f32, dim3(qn_pad / 128, (uint32_t)(nd / 128)), dim3(256), 0, st, d_Q,
-                           dx->d_P32 + d0 * dx->hp, d_S + d0, qn, n_left, dx->hp, ld);
+        const dim3 grid(qn_pad / 128, (uint32_t)(nd / 128));
+        if (raw)
+            hipLaunchKernelGGL(dense_scores_f32<1>, grid, dim3(256), 0, st, d_Q, P + d0 * dx->hp, d_S + d0, qn, n_left,
+                               dx->hp, ld);
+        else
+            hipLaunchKernelGGL(dense_scores_f32<0>, grid, dim3(256), 0, st, d_Q, P + d0 * dx->hp, d_S + d0, qn, n_left,
+                               dx->hp, ld);
         HIP_TRY(hipGetLastError());
     }
     return MSR_OK;
@@ -358,7 +364,7 @@ static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, u
         // the select instance: 1024 docs at 4096-doc tiles, 2048 at 8192); padding beyond that is never read
         const uint64_t round_docs = dx->tile_docs == 4096 ? 1024 : 2048;
         const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (dx->n + round_docs - 1) / round_docs * round_docs);
-        rc = dx->f32 ? launch_dense_gemm_f32(dx, (const float*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream)
+        rc = dx->f32 ? launch_dense_gemm_f32(dx, dx->d_P32, (const float*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream)
                      : launch_dense_gemm(dx, dx->d_P, (const _Float16*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream);
         if (rc != MSR_OK) break;
         (void)hipEventRecord(e1, dx->stream);
@@ -1383,8 +1389,13 @@ __global__ __launch_bounds__(256) void permute_rows(const uint4* __restrict__ sr
 
 }  // namespace msr
 
+// Bytes per row of a dense handle's passage rows and of its device query copy: h fp16 values, or hp f32 values (K zero
+// padded to a multiple of kF32KStep)
+static size_t dense_row_bytes(const msr_dense* dx) { return dx->f32 ? (size_t)dx->hp * 4 : (size_t)dx->h * 2; }
+
 // Passage rows in doc-ORDINAL order (P_ord[row2ord[r]] = P[r]), so that a query's row of GEMM output lines up with the
-// sparse accumulator tiles; built on first use, cached on the dense handle while the mapping is unchanged.
+// sparse accumulator tiles; in the handle's precision, built on first use, cached on the dense handle while the mapping
+// is unchanged.
 static int ensure_ordinal_rows(msr_dense* dx, hipStream_t stream, const uint32_t* row2ord, const uint64_t n) {
     if (!dx->d_P_ord || dx->ord_map.size() != n || memcmp(dx->ord_map.data(), row2ord, (size_t)n * 4) != 0) {
         std::vector<uint8_t> seen((size_t)n, 0);
@@ -1396,7 +1407,7 @@ static int ensure_ordinal_rows(msr_dense* dx, hipStream_t stream, const uint32_t
             seen[row2ord[r]] = 1;
         }
         uint32_t* d_map = nullptr;
-        const size_t bytes = (size_t)dx->n_pad * dx->h * 2;
+        const size_t row_bytes = dense_row_bytes(dx), bytes = (size_t)dx->n_pad * row_bytes;  // (row_bytes % 16 == 0)
         if (!dx->d_P_ord && hipMalloc(&dx->d_P_ord, bytes) != hipSuccess) {
             dx->d_P_ord = nullptr;
             set_error("hipMalloc of %zu bytes for the ordinal-ordered passage matrix failed", bytes);
@@ -1406,8 +1417,9 @@ static int ensure_ordinal_rows(msr_dense* dx, hipStream_t stream, const uint32_t
                   hipMemsetAsync(dx->d_P_ord, 0, bytes, stream) == hipSuccess &&
                   hipMemcpyAsync(d_map, row2ord, (size_t)n * 4, hipMemcpyHostToDevice, stream) == hipSuccess;
         if (ok && n) {
-            hipLaunchKernelGGL(permute_rows, dim3((uint32_t)n), dim3(256), 0, stream, reinterpret_cast<const uint4*>(dx->d_P),
-                               reinterpret_cast<uint4*>(dx->d_P_ord), d_map, dx->h / 8);
+            const void* src = dx->f32 ? (const void*)dx->d_P32 : (const void*)dx->d_P;
+            hipLaunchKernelGGL(permute_rows, dim3((uint32_t)n), dim3(256), 0, stream, reinterpret_cast<const uint4*>(src),
+                               reinterpret_cast<uint4*>(dx->d_P_ord), d_map, (uint32_t)(row_bytes / 16));
             ok = hipGetLastError() == hipSuccess;
         }
         ok = ok && hipStreamSynchronize(stream) == hipSuccess;
@@ -1429,26 +1441,54 @@ constexpr uint64_t kHybridChunkBytes = 160ull << 20;
 // What the fused and the multi-tile path share before their launches
 struct HybridSetup {
     msr_batch* b = nullptr;
-    _Float16* d_Q = nullptr;  // [nq rounded up to 256][h] queries, zero padded
+    uint8_t* d_Q = nullptr;   // [nq rounded up to 256] query rows of dense_row_bytes each, zero padded
     uint32_t* d_S = nullptr;  // score rows of one chunk
     bool ok = false;          // every scratch slot was taken and every upload enqueued
     ScoreArgs sa;             // every query of the batch; the hybrid kernels write their lists through ha
     HybridArgs ha;            // the fields that both paths use
 };
 
+// Rows [0, rows) of a host query matrix ([rows][h], fp16 or f32 as the handle holds) into a device copy of rows_pad rows
+// of dense_row_bytes: the padding rows, and on an f32 handle whose h is not a multiple of kF32KStep the padding columns,
+// zeroed (exactly neutral in either GEMM)
+static bool upload_query_rows(const msr_dense* dx, uint8_t* d_Q, const void* q, size_t rows, size_t rows_pad,
+                              hipStream_t st) {
+    const size_t q_row = dense_row_bytes(dx), h_row = (size_t)dx->h * (dx->f32 ? 4 : 2);
+    if (q_row == h_row)
+        return hipMemsetAsync(d_Q + rows * q_row, 0, (rows_pad - rows) * q_row, st) == hipSuccess &&
+               hipMemcpyAsync(d_Q, q, rows * h_row, hipMemcpyHostToDevice, st) == hipSuccess;
+    return hipMemsetAsync(d_Q, 0, rows_pad * q_row, st) == hipSuccess &&
+           hipMemcpy2DAsync(d_Q, q_row, q, h_row, h_row, rows, hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+// The hybrid paths' GEMM: f32 bit patterns of C = Q * P_ord^T (the ordinal-ordered rows) into out[q][ld] for doc
+// columns [0, n_cover), on the f32 MFMA for an f32 handle (the fmaf chain, 128 x 128 blocks), on the fp16 one otherwise
+// (256 x 256 blocks where H allows); Q rows padded to qn_pad, a multiple of hybrid_gemm_block(dx).
+static int launch_hybrid_gemm(msr_dense* dx, const uint8_t* d_Q, uint32_t* d_S, uint32_t qn, uint32_t qn_pad,
+                              uint64_t n_cover, uint64_t ld, hipStream_t st) {
+    if (dx->f32)
+        return launch_dense_gemm_f32(dx, (const float*)dx->d_P_ord, (const float*)d_Q, d_S, qn, qn_pad, n_cover, ld, st,
+                                     true);
+    return launch_dense_gemm(dx, (const _Float16*)dx->d_P_ord, (const _Float16*)d_Q, d_S, qn, qn_pad, n_cover, ld, st,
+                             true, true);
+}
+
+// Query rows per GEMM block edge, the unit in which both device-resident paths size their chunks
+static uint32_t hybrid_gemm_block(const msr_dense* dx) { return dx->f32 ? 128u : 256u; }
+
 // The ordinal-ordered passage rows, the query batch (created for `batch_k`), the query matrix, `s_bytes` of score rows
-// and the result lists out of the handle's scratch, the uploads of the queries and of self_ord, and both argument
-// blocks. A non-zero return is an error before the batch exists; s.ok == false is a failed slot or upload (the caller
-// reports it and still owns s.b).
+// and the result lists out of the handle's scratch, the uploads of the queries (q: [nq][h], fp16 or f32 as the handle
+// holds) and of self_ord, and both argument blocks. A non-zero return is an error before the batch exists; s.ok == false
+// is a failed slot or upload (the caller reports it and still owns s.b).
 static int hybrid_setup(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
-                        const uint16_t* q_fp16, int nq, int batch_k, int depth, int k, float alpha, uint32_t flags,
+                        const void* q, int nq, int batch_k, int depth, int k, float alpha, uint32_t flags,
                         const uint32_t* row2ord, const int32_t* self_ord, uint64_t ld, size_t s_bytes, HybridSetup& s) {
     DeviceIndex* d = ix->dev;
     if (int rc = ensure_ordinal_rows(dx, d->stream, row2ord, ix->host.h->n_docs)) return rc;
     if (int rc = msr_batch_create(ix, q_ptr, q_term, q_w, nq, batch_k, flags, &s.b)) return rc;
     const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
     const size_t perk = std::max<size_t>((size_t)nq * k, 1);
-    s.d_Q = (_Float16*)dx->take(msr_dense::S_Q, std::max<size_t>((size_t)nq_pad * dx->h * 2, 16));
+    s.d_Q = (uint8_t*)dx->take(msr_dense::S_Q, std::max<size_t>((size_t)nq_pad * dense_row_bytes(dx), 16));
     s.d_S = (uint32_t*)dx->take(msr_dense::S_S, s_bytes);
     uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perk * 4);
     float* d_sf = (float*)dx->take(msr_dense::S_SF, perk * 4);
@@ -1458,9 +1498,7 @@ static int hybrid_setup(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, cons
     if (ok && self_ord)
         ok = (d_self = (int32_t*)dx->take(msr_dense::S_SELF, std::max<size_t>(nq, 1) * 4)) != nullptr &&
              hipMemcpyAsync(d_self, self_ord, (size_t)nq * 4, hipMemcpyHostToDevice, d->stream) == hipSuccess;
-    if (ok && nq)
-        ok = hipMemsetAsync(s.d_Q + (size_t)nq * dx->h, 0, (size_t)(nq_pad - nq) * dx->h * 2, d->stream) == hipSuccess &&
-             hipMemcpyAsync(s.d_Q, q_fp16, (size_t)nq * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess;
+    if (ok && nq) ok = upload_query_rows(dx, s.d_Q, q, (size_t)nq, nq_pad, d->stream);
     s.ok = ok;
     fill_score_args(s.sa, s.b, k);
     s.sa.part = nullptr;
@@ -1492,7 +1530,7 @@ static int hybrid_download(const HybridArgs& ha, int nq, int k, uint32_t* out_or
 // The fused path of msr_hybrid_search (single-tile indexes, k <= 64): per chunk of queries (normally ONE chunk) a GEMM
 // launch on the ordinal-permuted passage matrix, then hybrid_tiles. ms = {fused scoring + selection + fusion kernel, dense GEMM, 0, 0}.
 static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
-                               const uint16_t* q_fp16, int nq, int depth, int k, float alpha, uint32_t flags,
+                               const void* q, int nq, int depth, int k, float alpha, uint32_t flags,
                                const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
                                int32_t* out_n, float ms[4]) {
     DeviceIndex* d = ix->dev;
@@ -1502,16 +1540,17 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     const uint32_t nt_threads = h->tile_docs == 4096 ? 256u : 512u;
     const uint64_t ld = (n + 4 * nt_threads - 1) / (4 * nt_threads) * (4 * nt_threads);  // whole select rounds
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (n + 255) / 256 * 256);
-    const uint32_t col_blocks = (uint32_t)(n_cover / 256);
-    const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
-    // queries per chunk: whole rounds of the chip's 256 CUs worth of 256 x 256 GEMM blocks, score rows <= ~160 MB so
+    const uint32_t gb = hybrid_gemm_block(dx);  // 256 x 256 fp16 blocks, 128 x 128 f32 blocks
+    const uint32_t col_blocks = (uint32_t)(n_cover / gb);
+    const uint32_t nq_pad = (uint32_t)((nq + gb - 1) / gb * gb);
+    // queries per chunk: whole rounds of the chip's 256 CUs worth of GEMM blocks, score rows <= ~160 MB so
     // that hybrid_tiles finds its row in the Infinity Cache (the row load is a dependent fetch at the start of the
     // epilogue: from HBM the same kernel measured 1.66 ms instead of 1.30 ms per 25 010 queries)
-    uint64_t row_blocks = std::max<uint64_t>(1, kHybridChunkBytes / (ld * 4 * 256));
+    uint64_t row_blocks = std::max<uint64_t>(1, kHybridChunkBytes / (ld * 4 * gb));
     if (col_blocks && row_blocks * col_blocks >= 256) row_blocks = row_blocks * col_blocks / 256 * 256 / col_blocks;
-    const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * 256, std::max<uint32_t>(nq_pad, 256u));
+    const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * gb, std::max<uint32_t>(nq_pad, gb));
     HybridSetup s;
-    if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, k, depth, k, alpha, flags, row2ord, self_ord, ld,
+    if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q, nq, k, depth, k, alpha, flags, row2ord, self_ord, ld,
                                (size_t)qc * ld * 4, s))
         return rc0;
     ScoreArgs& sa = s.sa;
@@ -1524,7 +1563,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     std::vector<hipEvent_t> ev;
     for (uint32_t q0 = 0; q0 < (uint32_t)nq && rc == MSR_OK; q0 += qc) {
         const uint32_t qn = std::min<uint32_t>(qc, (uint32_t)nq - q0);
-        const uint32_t qn_pad = (qn + 255) / 256 * 256;
+        const uint32_t qn_pad = (qn + gb - 1) / gb * gb;
         hipEvent_t e[3] = {nullptr, nullptr, nullptr};
         for (auto& x : e) {
             if (hipEventCreate(&x) != hipSuccess) rc = MSR_E_HIP;
@@ -1535,8 +1574,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
             break;
         }
         (void)hipEventRecord(e[0], d->stream);
-        rc = launch_dense_gemm(dx, dx->d_P_ord, s.d_Q + (size_t)q0 * dx->h, s.d_S, qn, qn_pad, n_cover, ld, d->stream, true,
-                               true);
+        rc = launch_hybrid_gemm(dx, s.d_Q + (size_t)q0 * dense_row_bytes(dx), s.d_S, qn, qn_pad, n_cover, ld, d->stream);
         if (rc != MSR_OK) break;
         (void)hipEventRecord(e[1], d->stream);
         sa.q0 = q0;
@@ -1598,7 +1636,7 @@ static uint32_t tile_quota(uint64_t tile_docs, uint64_t n, uint32_t depth) {
 // hybrid_tiles<MODE 1> over (query, tile) and hybrid_fuse_query over the queries; flagged queries (normally none) are
 // repeated with quota = depth. ms = {candidate kernel, dense GEMM, 0, fusion kernel}.
 static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term,
-                                   const int32_t* q_w, const uint16_t* q_fp16, int nq, int depth, int k, float alpha,
+                                   const int32_t* q_w, const void* q, int nq, int depth, int k, float alpha,
                                    uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord,
                                    float* out_score, int32_t* out_n, float ms[4]) {
     DeviceIndex* d = ix->dev;
@@ -1608,15 +1646,16 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     HIP_TRY(hipSetDevice(d->device));
     const uint64_t ld = (uint64_t)n_tiles * tile;  // a query's score row: tile t starts at column t * tile
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (n + 255) / 256 * 256);
-    const uint32_t col_blocks = (uint32_t)(n_cover / 256);
-    const uint32_t nq_pad = (uint32_t)((nq + 255) / 256 * 256);
+    const uint32_t gb = hybrid_gemm_block(dx);  // 256 x 256 fp16 blocks, 128 x 128 f32 blocks
+    const uint32_t col_blocks = (uint32_t)(n_cover / gb);
+    const uint32_t nq_pad = (uint32_t)((nq + gb - 1) / gb * gb);
     // queries per chunk: score rows of ~160 MB (they are read back out of the Infinity Cache), whole rounds of the
     // chip's 256 CUs worth of GEMM blocks (the bytes that travel are the n_cover written columns of a row, not its
     // padded stride). Among the chunk sizes that fit, the one whose GEMM grid fills its last round of 256 CUs best:
     // 2 x 98 blocks leave a quarter of the chip idle, 5 x 98 = 490 fill 1.91 rounds
-    const uint64_t rb_max = std::max<uint64_t>(1, kHybridChunkBytes / (std::max<uint64_t>(n_cover, 256) * 4 * 256));
-    const uint64_t row_blocks = pick_row_blocks(col_blocks, rb_max, nq_pad / 256);
-    const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * 256, std::max<uint32_t>(nq_pad, 256u));
+    const uint64_t rb_max = std::max<uint64_t>(1, kHybridChunkBytes / (std::max<uint64_t>(n_cover, gb) * 4 * gb));
+    const uint64_t row_blocks = pick_row_blocks(col_blocks, rb_max, nq_pad / gb);
+    const uint32_t qc = (uint32_t)std::min<uint64_t>(row_blocks * gb, std::max<uint32_t>(nq_pad, gb));
     const uint64_t last_docs = n - (uint64_t)(n_tiles - 1) * tile;
     const uint32_t quota_full = n_tiles > 1 ? tile_quota(tile, n, (uint32_t)depth) : tile_quota(n, n, (uint32_t)depth);
     const uint32_t quota_last = n_tiles > 1 ? std::min(quota_full, tile_quota(last_docs, n, (uint32_t)depth)) : quota_full;
@@ -1625,7 +1664,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     // record slots (a tile's union of two candidate sets: 2 x quota): a chunk of the first round or at least ONE row of the second
     const size_t cand_slots = 2 * std::max<size_t>((size_t)qc * per_tile_row * quota_full, per_tile_row * (size_t)depth);
     HybridSetup s;  // (a batch for k = 1: only its query arrays are used)
-    if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, 1, depth, k, alpha, flags, row2ord, self_ord, ld,
+    if (int rc0 = hybrid_setup(ix, dx, q_ptr, q_term, q_w, q, nq, 1, depth, k, alpha, flags, row2ord, self_ord, ld,
                                (size_t)qc * ld * 4, s))
         return rc0;
     ScoreArgs& sa = s.sa;
@@ -1651,10 +1690,10 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     ha.quota_last = quota_last;
     ha.flags = d_flags;
     // one pass of the three kernels over `rows` launch rows (queries q0 .. or the listed ones), dense rows from d_Qrows
-    auto launch_rows = [&](const _Float16* d_Qrows, uint32_t rows, uint32_t q0, hipEvent_t* e) -> int {
-        const uint32_t rows_pad = (rows + 255) / 256 * 256;
+    auto launch_rows = [&](const uint8_t* d_Qrows, uint32_t rows, uint32_t q0, hipEvent_t* e) -> int {
+        const uint32_t rows_pad = (rows + gb - 1) / gb * gb;
         if (e) (void)hipEventRecord(e[0], d->stream);
-        int r2 = launch_dense_gemm(dx, dx->d_P_ord, d_Qrows, s.d_S, rows, rows_pad, n_cover, ld, d->stream, true, true);
+        int r2 = launch_hybrid_gemm(dx, d_Qrows, s.d_S, rows, rows_pad, n_cover, ld, d->stream);
         if (r2 != MSR_OK) return r2;
         if (e) (void)hipEventRecord(e[1], d->stream);
         sa.q0 = q0;
@@ -1713,7 +1752,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
             rc = MSR_E_HIP;
             break;
         }
-        rc = launch_rows(s.d_Q + (size_t)q0 * dx->h, qn, q0, e);
+        rc = launch_rows(s.d_Q + (size_t)q0 * dense_row_bytes(dx), qn, q0, e);
     }
     std::vector<uint32_t> hflags((size_t)nq, 0);
     if (rc == MSR_OK && nq &&
@@ -1728,18 +1767,18 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
         if (hflags[(size_t)i]) redo.push_back((uint32_t)i);
     if (rc == MSR_OK && !redo.empty()) {
         const uint32_t rows_cap = (uint32_t)std::min<size_t>(std::min<size_t>(cand_slots / (2 * per_tile_row * (size_t)depth), qc), redo.size());
-        std::vector<uint16_t> qrows((size_t)rows_cap * dx->h);
+        const size_t h_row = (size_t)dx->h * (dx->f32 ? 4 : 2);  // bytes per row of the caller's query matrix
+        std::vector<uint8_t> qrows((size_t)rows_cap * h_row);
         ha.quota_full = ha.quota_last = (uint32_t)depth;
         ha.stride = 2 * (uint32_t)depth;
         ha.qlist = d_qlist;
         for (size_t at = 0; at < redo.size() && rc == MSR_OK; at += rows_cap) {
             const uint32_t rows = (uint32_t)std::min<size_t>(rows_cap, redo.size() - at);
-            const uint32_t rows_pad = (rows + 255) / 256 * 256;
+            const uint32_t rows_pad = (rows + gb - 1) / gb * gb;
             for (uint32_t r = 0; r < rows; ++r)
-                memcpy(qrows.data() + (size_t)r * dx->h, q_fp16 + (size_t)redo[at + r] * dx->h, (size_t)dx->h * 2);
+                memcpy(qrows.data() + (size_t)r * h_row, (const uint8_t*)q + (size_t)redo[at + r] * h_row, h_row);
             // (d_Q's first rows are reused: the first round is over)
-            ok = hipMemsetAsync(s.d_Q, 0, (size_t)rows_pad * dx->h * 2, d->stream) == hipSuccess &&
-                 hipMemcpyAsync(s.d_Q, qrows.data(), (size_t)rows * dx->h * 2, hipMemcpyHostToDevice, d->stream) == hipSuccess &&
+            ok = upload_query_rows(dx, s.d_Q, qrows.data(), rows, rows_pad, d->stream) &&
                  hipMemcpyAsync(d_qlist, redo.data() + at, (size_t)rows * 4, hipMemcpyHostToDevice, d->stream) == hipSuccess;
             if (!ok) {
                 set_error("upload failed in the second round of msr_hybrid_search");
@@ -1793,19 +1832,13 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     return rc;
 }
 
-extern "C" {
-
-int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
-                      const uint16_t* q_fp16, int nq, int depth, int k, float alpha, uint32_t flags,
-                      const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n,
-                      float ms[4]) {
-    if (!ix || !dx || !row2ord || !out_ord || !out_score || !out_n || nq < 0) {
-        set_error("msr_hybrid_search: bad argument");
-        return MSR_E_INVAL;
-    }
-    if (dx->f32) {
-        set_error("msr_hybrid_search: the dense handle holds f32 rows (msr_dense_open_f32); the hybrid path takes an fp16 "
-                  "handle (msr_dense_open)");
+// msr_hybrid_search and msr_hybrid_search_f32 after their precision check: q is [nq][h] in the handle's precision
+static int hybrid_search_impl(const char* fn, msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term,
+                              const int32_t* q_w, const void* q, int nq, int depth, int k, float alpha, uint32_t flags,
+                              const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
+                              int32_t* out_n, float ms[4]) {
+    if (!ix || !dx || !row2ord || !out_ord || !out_score || !out_n || nq < 0 || (nq && !q)) {
+        set_error("%s: bad argument", fn);
         return MSR_E_INVAL;
     }
     if (!ix->dev) {
@@ -1828,13 +1861,15 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
     DeviceIndex* d = ix->dev;
     const IndexHeader* h = ix->host.h;
     static const bool no_fused = getenv("MSR_NO_FUSED_HYBRID") != nullptr;  // diagnostic: force the list-based path
-    if (!no_fused && h->n_tiles == 1 && ix->shard_ntiles == 1 && ix->term_nshards == 0 && k <= 64 && dx->h % 8 == 0 &&
+    // (permute_rows moves uint4: an fp16 row needs h % 8 == 0; an f32 row of hp floats always qualifies)
+    const bool rows_ok = dx->f32 || dx->h % 8 == 0;
+    if (!no_fused && h->n_tiles == 1 && ix->shard_ntiles == 1 && ix->term_nshards == 0 && k <= 64 && rows_ok &&
         (h->tile_docs == 4096 || h->tile_docs == 8192))
-        return hybrid_search_fused(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, depth, k, alpha, flags, row2ord, self_ord,
+        return hybrid_search_fused(ix, dx, q_ptr, q_term, q_w, q, nq, depth, k, alpha, flags, row2ord, self_ord,
                                    out_ord, out_score, out_n, ms);
-    if (!no_fused && ix->shard_ntiles == h->n_tiles && ix->term_nshards == 0 && dx->h % 8 == 0 && h->n_tiles <= kMaxGridY &&
+    if (!no_fused && ix->shard_ntiles == h->n_tiles && ix->term_nshards == 0 && rows_ok && h->n_tiles <= kMaxGridY &&
         (h->tile_docs == 4096 || h->tile_docs == 8192))
-        return hybrid_search_multitile(ix, dx, q_ptr, q_term, q_w, q_fp16, nq, depth, k, alpha, flags, row2ord, self_ord,
+        return hybrid_search_multitile(ix, dx, q_ptr, q_term, q_w, q, nq, depth, k, alpha, flags, row2ord, self_ord,
                                        out_ord, out_score, out_n, ms);
     msr_batch* b = nullptr;
     int rc = msr_batch_create(ix, q_ptr, q_term, q_w, nq, depth, flags, &b);
@@ -1866,7 +1901,7 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
     // fuse_tiles takes both top-depth lists as SETS (min, max, membership): single-tile indexes skip the ranking
     b->unsorted_ok = true;
     if (rc == MSR_OK) rc = batch_search_local(b, depth, false);  // sparse top-depth keys -> b->d_keys
-    if (rc == MSR_OK) rc = dense_search_impl(dx, q_fp16, nq, depth, d_didx, d_dkey, d_dn, &t_gemm, &t_sel, true, true);
+    if (rc == MSR_OK) rc = dense_search_impl(dx, q, nq, depth, d_didx, d_dkey, d_dn, &t_gemm, &t_sel, true, true);
     if (rc == MSR_OK) {
         (void)hipEventRecord(e0, d->stream);
         FuseArgs fa;
@@ -1941,6 +1976,33 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
     if (e1) (void)hipEventDestroy(e1);
     batch_free(b);
     return rc;
+}
+
+extern "C" {
+
+int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                      const uint16_t* q_fp16, int nq, int depth, int k, float alpha, uint32_t flags,
+                      const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n,
+                      float ms[4]) {
+    if (dx && dx->f32) {
+        set_error("msr_hybrid_search: the dense handle holds f32 rows (msr_dense_open_f32); search it with "
+                  "msr_hybrid_search_f32, or open an fp16 handle (msr_dense_open)");
+        return MSR_E_INVAL;
+    }
+    return hybrid_search_impl("msr_hybrid_search", ix, dx, q_ptr, q_term, q_w, q_fp16, nq, depth, k, alpha, flags, row2ord,
+                              self_ord, out_ord, out_score, out_n, ms);
+}
+
+int msr_hybrid_search_f32(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                          const float* q, int nq, int depth, int k, float alpha, uint32_t flags, const uint32_t* row2ord,
+                          const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n, float ms[4]) {
+    if (dx && !dx->f32) {
+        set_error("msr_hybrid_search_f32: the dense handle holds fp16 rows (msr_dense_open); search it with "
+                  "msr_hybrid_search, or open an f32 handle (msr_dense_open_f32)");
+        return MSR_E_INVAL;
+    }
+    return hybrid_search_impl("msr_hybrid_search_f32", ix, dx, q_ptr, q_term, q_w, q, nq, depth, k, alpha, flags, row2ord,
+                              self_ord, out_ord, out_score, out_n, ms);
 }
 
 }  // extern "C"

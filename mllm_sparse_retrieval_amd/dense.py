@@ -7,7 +7,8 @@ Drop-in for tevatron's FaissFlatSearcher as src/search.py uses it:
 The reference's hybrid run keeps the vectors in fp16 on the GPU (co.useFloat16, src/search.py:257,267); so does this
 class by default, with f32 accumulation on MFMA (msr_dense_search). Its other runs (no --use_gpu, src/arguments.py:63)
 search a plain f32 IndexFlatIP on the CPU: precision="f32" is that search (msr_dense_search_f32), every score the
-k-ordered fmaf chain of f32 inputs. Ties in score are broken by the lower row index.
+k-ordered fmaf chain of f32 inputs; hybrid_search_f32 is the hybrid search on such a handle. Ties in score are broken by
+the lower row index.
 """
 from __future__ import annotations
 
@@ -193,25 +194,46 @@ def hybrid_search(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, 
                   drop_df_eq_n=True):
     """Sparse top-`depth` + dense top-`depth` + min-max fusion (src/hybrid.py:32-53, weights [alpha, 1-alpha]) + top-k,
     all on the GPU. -> (doc ordinals uint32 [nq,k], fused scores float32 [nq,k], n [nq], kernel ms per stage)."""
+    if getattr(dense_index, "precision", "fp16") != "fp16":
+        raise ValueError("hybrid_search takes an fp16 DenseIndex (the reference's hybrid run uses --use_gpu, fp16 "
+                         f"storage); this one holds {dense_index.precision} rows: search it with hybrid_search_f32")
+    q16 = _as_fp16_rows(q_reps, dense_index.dim, dense_index)   # (consumed by the synchronous call below)
+    return _hybrid_call(lib().msr_hybrid_search, sparse_index, dense_index, q_ptr, q_term, q_w, q16.view(np.uint16),
+                        depth, k, alpha, row2ord, self_ord, drop_df_eq_n)
+
+
+def hybrid_search_f32(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k, alpha, row2ord, self_ord=None,
+                      drop_df_eq_n=True):
+    """hybrid_search with the dense side in f32 (DenseIndex(precision="f32"): the reference's default, an f32
+    IndexFlatIP without --use_gpu, src/arguments.py:63): every dense score is the k-ordered fmaf chain, bit-equal to
+    DenseIndex.search_keys on the same handle. Same arguments and return value as hybrid_search."""
+    if getattr(dense_index, "precision", "fp16") != "f32":
+        raise ValueError("hybrid_search_f32 takes an f32 DenseIndex (precision=\"f32\"); this one holds "
+                         f"{getattr(dense_index, 'precision', 'fp16')} rows: search it with hybrid_search")
+    q32 = _as_f32_rows(q_reps, dense_index.dim)
+    return _hybrid_call(lib().msr_hybrid_search_f32, sparse_index, dense_index, q_ptr, q_term, q_w, q32, depth, k, alpha,
+                        row2ord, self_ord, drop_df_eq_n)
+
+
+def _hybrid_call(fn, sparse_index, dense_index, q_ptr, q_term, q_w, q, depth, k, alpha, row2ord, self_ord, drop_df_eq_n):
+    """One msr_hybrid_search / msr_hybrid_search_f32 call on query rows `q` already in the handle's precision."""
     from . import _cabi
     from ._cabi import MSR_F_DROP_DF_EQ_N
 
-    if getattr(dense_index, "precision", "fp16") != "fp16":
-        raise ValueError("hybrid_search takes an fp16 DenseIndex (the reference's hybrid run uses --use_gpu, fp16 "
-                         f"storage); this one holds {dense_index.precision} rows")
     q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
-    q16 = _as_fp16_rows(q_reps, dense_index.dim, dense_index)   # (consumed by the synchronous call below)
     nq = len(q_ptr) - 1
-    if q16.shape[0] != nq:
+    if q.shape[0] != nq:
         raise ValueError("sparse and dense query counts differ")
     row2ord = np.ascontiguousarray(row2ord, dtype=np.uint32)
+    if row2ord.shape != (dense_index.n,):
+        raise ValueError(f"row2ord needs one ordinal per dense row ({dense_index.n}), got shape {row2ord.shape}")
     so = None if self_ord is None else np.ascontiguousarray(self_ord, dtype=np.int32)
+    if so is not None and so.shape != (nq,):
+        raise ValueError(f"self_ord needs one entry per query ({nq}), got shape {so.shape}")
     ords = np.empty((nq, k), dtype=np.uint32)
     sc = np.empty((nq, k), dtype=np.float32)
     n = np.zeros(nq, dtype=np.int32)
     ms = (C.c_float * 4)()
-    check(lib().msr_hybrid_search(sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w),
-                                  ptr(q16.view(np.uint16)), nq, int(depth), int(k), float(alpha),
-                                  MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so), ptr(ords), ptr(sc),
-                                  ptr(n), ms))
+    check(fn(sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w), ptr(q), nq, int(depth), int(k),
+             float(alpha), MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so), ptr(ords), ptr(sc), ptr(n), ms))
     return ords, sc, n, dict(sparse=ms[0], dense_gemm=ms[1], dense_select=ms[2], fusion=ms[3])

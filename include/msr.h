@@ -287,6 +287,35 @@ int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const 
 int msr_hybrid_search_f32(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
                           const float* q, int nq, int depth, int k, float alpha, uint32_t flags, const uint32_t* row2ord,
                           const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n, float ms[4]);
+/* ---- the whole fused union and both depth lists from one call: what the reference's hybrid run writes per query — the
+ * sparse top-`depth` list, the dense top-`depth` list and fuse() of the two, which keeps EVERY doc of either list
+ * (src/search.py:455-461, src/hybrid.py:32-53) — plus, per fused doc, the list(s) it came from (fuse_statistic,
+ * src/hybrid.py:56-90). Inputs mean what they mean for msr_hybrid_search / msr_hybrid_search_f32; q is [nq][h] fp16
+ * (q_is_f32 = 0, dx from msr_dense_open) or f32 (q_is_f32 = 1, dx from msr_dense_open_f32), a mismatch is MSR_E_INVAL.
+ * 1 <= depth <= MSR_KMAX; there is no k. Every per-member output is row-major [nq][2 * depth]; row i holds out_n[i]
+ * members = the union of query i's two depth lists minus self_ord[i], by fused score descending (ties: lower ordinal);
+ * a member whose fused score is 0 (the depth-th doc of one list that is not in the other) IS a member. Padding:
+ * 0xFFFFFFFF / 0.f as msr_hybrid_search pads, 0 in the optional arrays.
+ *   out_score       the f32 fused score of msr_hybrid_search[_f32]: the first min(k, out_n[i]) entries of a row have the
+ *                   ordinals and the score bits those calls return for that k on their candidate path;
+ *   out_src         bit 0: in the dense depth list, bit 1: in the sparse depth list (1 / 2 / 3 = fuse_statistic's
+ *                   'dense' / 'sparse' / 'fuse' with runs ordered [dense, sparse], src/search.py:459);
+ *   out_sparse_u32  the exact sparse score where bit 1 is set, else 0;
+ *   out_dense       the f32 dense score where bit 0 is set, else 0 (f32 handle: the bits of msr_dense_search_f32);
+ *   out_range[i]    {dense max, dense min, sparse max, sparse min}: the best and the depth-th (or last) score of each
+ *                   UNFILTERED list, which the fusion normalises with and get_run_dict stores (src/search.py:76-81);
+ *                   {0, 0} for an empty list. Not recoverable from the members when self_ord[i] was the best or the last.
+ * The four optional outputs may be NULL: such an array is neither computed into host memory nor downloaded.
+ * ms = {candidate kernel, dense GEMM, 0, fusion kernel}. Supported handles: those of msr_hybrid_search's candidate path
+ * (whole index, 4096- or 8192-doc tiles, fp16: h % 8 == 0), a single-tile index included; any other handle is refused
+ * with MSR_E_INVAL (no list-based union; MSR_NO_FUSED_HYBRID is not read). Dense ties at the depth boundary: lower
+ * ordinal. Scratch stays on the dense handle and only grows. */
+#define MSR_UNION_MAX (2 * MSR_KMAX) /* most docs a fused union can hold */
+int msr_hybrid_search_union(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                            const void* q, int q_is_f32, int nq, int depth, float alpha, uint32_t flags,
+                            const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
+                            int32_t* out_n, uint8_t* out_src, uint32_t* out_sparse_u32, float* out_dense, float* out_range,
+                            float ms[4]);
 
 /* ---- encode-side sparsifier: log(1 + relu(logit)) -> top-k -> rint(x * 100) (src/model.py:104, src/encode.py:69-75).
  * logits: row-major [rows][vocab], f32 (is_f16 = 0) or IEEE fp16 (is_f16 = 1). fp16_math = 1 rounds 1 + relu and the

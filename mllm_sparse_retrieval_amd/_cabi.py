@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libmsr.so")
 MSR_OK = 0
 MSR_F_DROP_DF_EQ_N = 1
 MSR_KMAX = 1024
+MSR_UNION_MAX = 2 * MSR_KMAX
 MSR_COMM_ID_BYTES = 128
 
 _ERR_NAMES = {
@@ -95,6 +96,8 @@ SYMBOLS = [
     ("msr_f32_to_f16", _I, [_VP, _VP, _U64, _I]),
     ("msr_hybrid_search", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_hybrid_search_f32", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("msr_hybrid_search_union", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     _VP, _VP, _VP, _VP]),
     ("msr_sparsify", _I, [_VP, _I, _I, _I, _U32, _I, _I, _VP, _VP, _VP]),
     ("msr_synth_vectors", _I, [_U64, _U32, _U32, C.c_double, _U64, _I, _VP, _VP, _VP]),
     ("msr_last_error", _CP, []),

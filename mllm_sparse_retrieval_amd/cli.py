@@ -128,6 +128,27 @@ def _check_search_args(a):
                      "index, --hybrid_f32 its f32 CPU index)")
         if a.sparse_index is None or a.passage_reps is None:
             sys.exit("search: --hybrid_f32 applies to hybrid search: give both --passage_reps and --sparse_index")
+    if getattr(a, "fusion_union", False):
+        if a.host_fusion:
+            sys.exit("search: --fusion_union and --host_fusion contradict each other (--fusion_union is one "
+                     "msr_hybrid_search_union call on the GPU, --host_fusion the reference's loop with fuse() on the host)")
+        if a.sparse_index is None or a.passage_reps is None:
+            sys.exit("search: --fusion_union applies to hybrid search: give both --passage_reps and --sparse_index")
+        if not 1 <= a.depth <= MSR_KMAX:
+            sys.exit(f"search: --fusion_union needs --depth in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth}; it is not "
+                     "clamped under this flag): lower --depth, or use --host_fusion")
+        from .index import SparseIndex
+
+        with SparseIndex(_index_path(a.sparse_index), device=-1) as meta:  # host-side metadata only: no GPU work
+            if meta.tile_docs not in (4096, 8192):
+                sys.exit(f"search: --fusion_union needs an index with 4096- or 8192-doc tiles, {a.sparse_index} has "
+                         f"{meta.tile_docs}: rebuild it with --tile_docs 4096 / 8192, or use --host_fusion")
+
+
+def _index_path(sparse_index):
+    """--sparse_index names the directory the index step wrote (its `index` entry) or the index itself."""
+    inner = os.path.join(sparse_index, "index")
+    return inner if os.path.isdir(inner) else sparse_index
 
 
 def _cmd_search(a):
@@ -177,8 +198,7 @@ def _cmd_search(a):
             qids = wanted
         texts = [""] * len(qids)
     else:
-        searcher = LuceneImpactSearcher(os.path.join(a.sparse_index, "index") if os.path.isdir(
-            os.path.join(a.sparse_index, "index")) else a.sparse_index, None, device=a.device)
+        searcher = LuceneImpactSearcher(_index_path(a.sparse_index), None, device=a.device)
         searcher.set_analyzer(JWhiteSpaceAnalyzer())
         qids, texts = read_queries(a.queries or os.path.join(a.sparse_index, "query.tsv"))
     n_queries = len(qids)
@@ -291,12 +311,15 @@ def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
     reference also reports (src/metrices.py:105-126) come from one whole-shard call each. Returns the three run dicts in
     the reference's layouts (src/search.py:66-82; the fused run without the 'docs' level, src/hybrid.py:32-53).
     --hybrid_f32: an f32 DenseIndex and hybrid_search_f32 (the reference's f32 flat index) instead of fp16.
+    --fusion_union: ONE msr_hybrid_search_union call instead, from which all three runs come (fusion.union_to_runs): the
+    fused run holds the WHOLE union as the reference's does, and nothing is scored a second time.
     Difference to --host_fusion: the fused run holds the best --fusion_k docs of the union (the recall reporter reads
     200, src/metrices.py:9), and an exact tie of two DENSE scores at the depth boundary goes to the lower doc ordinal
     instead of the lower row (include/msr.h)."""
     import numpy as np
 
-    from .dense import DenseIndex, hybrid_search, hybrid_search_f32, row_to_ordinal
+    from .dense import DenseIndex, hybrid_search, hybrid_search_f32, hybrid_search_union, row_to_ordinal
+    from .fusion import union_to_runs
     from .run import get_run_dict
 
     ix = searcher.index
@@ -314,6 +337,11 @@ def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
         r2o = np.asarray([ord_of[str(x)] for x in p_lookup], dtype=np.uint32)
         self_ord = np.asarray([ord_of.get(x, -1) for x in qids], dtype=np.int32) if a.remove_query else None
         drop = searcher.min_idf >= 0 if searcher.drop_df_eq_n is None else bool(searcher.drop_df_eq_n)
+        if getattr(a, "fusion_union", False):
+            ords, fs, cnt, src, su, de, rng, _ = hybrid_search_union(ix, dix, q_ptr, q_term, q_w, q, depth, a.alpha, r2o,
+                                                                     self_ord, drop_df_eq_n=drop,
+                                                                     with_lists=not a.fusion_only)
+            return union_to_runs(qids, table, ords, cnt, fs, src, su, de, rng)
         ords, fs, cnt, _ = hybrid(ix, dix, q_ptr, q_term, q_w, q, depth, k_f, a.alpha, r2o, self_ord, drop_df_eq_n=drop)
         fs_rows = fs.tolist()
         fusion_run = {qid: dict(zip(table[ords[i, :cnt[i]]].tolist(), fs_rows[i][:cnt[i]])) for i, qid in enumerate(qids)}
@@ -421,8 +449,15 @@ def main(argv=None):
                    help="hybrid: f32 dense side (the reference's default f32 flat index, no --use_gpu) on both the GPU "
                         "route (msr_hybrid_search_f32) and --host_fusion, instead of fp16 storage; needs --passage_reps "
                         "and --sparse_index, refused with --use_gpu")
-    s.add_argument("--fusion_k", type=int, default=1000, help="hybrid on the GPU: docs kept of each query's fused union (<= 1024)")
-    s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs")
+    s.add_argument("--fusion_k", type=int, default=1000, help="hybrid on the GPU: docs kept of each query's fused union "
+                                                              "(<= 1024); ignored under --fusion_union")
+    s.add_argument("--fusion_union", action="store_true",
+                   help="hybrid on the GPU: ONE msr_hybrid_search_union call for the whole query file; fusion.trec holds "
+                        "the WHOLE union of both depth lists (up to 2 x --depth docs per query, as the reference's fuse() "
+                        "keeps them) and sparse.trec / dense.trec come from the same call; with --hybrid_f32 on the f32 "
+                        "handle; --depth <= 1024, not with --host_fusion, --fusion_k is ignored")
+    s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs (with or without --fusion_union; "
+                                                                   "the fused run then feeds the recall report only: fusion.trec is written beside a dense run)")
     s.add_argument("--compat-denominator", "--compat_denominator", dest="compat_denominator", action="store_true",
                    help="multi-rank: keep the sampler's padded repeats and divide by len(shard) * world like the reference")
     s.set_defaults(fn=_cmd_search)

@@ -131,7 +131,8 @@ struct msr_dense {
     bool lds_attr_set = false;  // dense_scores_256k needs the 128 KiB dynamic-LDS opt-in once per device
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
     // grown: six hipMalloc / hipFree pairs of up to 200 MB cost a call more than its kernels
-    enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_COUNT };
+    enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_USRC, S_USPARSE, S_UDENSE,
+                S_URANGE, S_COUNT };
     void* scratch[S_COUNT] = {};
     size_t scratch_bytes[S_COUNT] = {};
     uint64_t n_device_allocs = 0;  // hipMalloc calls made on behalf of this handle (steady-state calls make none)
@@ -1240,11 +1241,29 @@ __device__ __forceinline__ uint64_t kth_largest_u64(Each each, uint32_t need, Kt
 // (src/hybrid.py:32-53: min = the depth-th score, max = the best, of the UNFILTERED lists, src/search.py:76-81; the
 // query's own doc skipped, src/search.py:72-74) — a record carries both of its doc's scores, so there is nothing to
 // join — and the top-k of the fused scores (ties: lower ordinal). k <= 1024, depth <= 1024.
-template <int NT, int EPT /* records per thread held in registers */>
-__global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, const uint32_t q0) {
+//
+// UNION = true (msr_hybrid_search_union; `u` is read by these instances only, the others are launched with an unused
+// one): the same kernel up to the fused keys, then NO top-k selection: every non-zero fused key (<= 2 x depth <= 2 048)
+// is collected and sorted, h.k = 2 x depth is the row length of the outputs, and the records stay in the registers beside
+// their fused keys, because the optional per-member outputs need them again after the sort: a sorted key carries the
+// ordinal, not the record slot, so each thread walks its records once more and finds every member's rank by a binary
+// search of its (unique) fused key in the sorted LDS array (<= 11 probes per member, ~2 000 members over 256 or 512
+// threads) — no slot array to carry through the sort, no second sort.
+
+// The four optional outputs of msr_hybrid_search_union on the device (null = not wanted)
+struct UnionOut {
+    uint8_t* src;      // [nq][2 x depth] bit 0: in the dense depth list, bit 1: in the sparse depth list
+    uint32_t* sparse;  // [nq][2 x depth] exact sparse score where bit 1 is set, else 0
+    float* dense;      // [nq][2 x depth] dense score where bit 0 is set, else 0
+    float* range;      // [nq][4] {dense max, dense min, sparse max, sparse min} of the unfiltered depth lists
+};
+
+template <int NT, int EPT /* records per thread held in registers */, bool UNION = false>
+__global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, const uint32_t q0, const UnionOut u) {
     static_assert(NT >= 256 && NT % 64 == 0 && NT / 64 <= 16, "scratch layout");
-    __shared__ __attribute__((aligned(16))) uint64_t cand[kCandCap];
-    __shared__ __attribute__((aligned(16))) uint64_t res[kCandCap];
+    constexpr int CAP = UNION ? 2 * kCandCap : kCandCap;  // (a power of two: rank_and_emit's bitonic sort pads to one)
+    __shared__ __attribute__((aligned(16))) uint64_t cand[CAP];
+    __shared__ __attribute__((aligned(16))) uint64_t res[CAP];
     __shared__ __attribute__((aligned(16))) KthScratch ks;
     __shared__ uint32_t red[4];             // present sparse scores, docs, invalid flag, collected keys
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -1340,7 +1359,7 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
         if (in_s) f += h.w_sparse * ((sv == smax_u && spread_s) ? 1.0f : ((float)sv - smin) * inv_sden);
         return ((uint64_t)f32_to_key(f) << 32) | (uint64_t)(0xFFFFFFFFu - o);
     };
-    // the fused keys replace the records in the registers (16 x u64 for 48 x u32)
+    // the fused keys replace the records in the registers (16 x u64 for 48 x u32; UNION keeps both)
     uint64_t fk[EPT];
 #pragma unroll
     for (int e = 0; e < EPT; ++e) fk[e] = in_regs ? fused_key(ro[e], rs[e], rd[e]) : 0ull;
@@ -1352,18 +1371,31 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
             for (uint32_t i = tid; i < n_slots; i += NT) f(fused_key(g_ord[i], g_s[i], g_d[i]));
         }
     };
-    // ---- top-k of the fused scores over the union (ties: lower ordinal)
-    uint32_t members;
-    uint64_t mx_f;
-    const uint64_t T_f = kth_largest_u64<NT>(each_f, h.k, ks, tid, &members, &mx_f);
-    const uint32_t n_out = min(h.k, members);
-    each_f([&](const uint64_t key) {
-        if (key && key >= T_f) {
-            const uint32_t pos = atomicAdd(&red[3], 1u);
-            if (pos < (uint32_t)kCandCap) cand[pos] = key;
-        }
-    });
-    __syncthreads();
+    uint32_t n_out;
+    if constexpr (UNION) {
+        // ---- the whole union: every member's key, sorted (ties: lower ordinal)
+        each_f([&](const uint64_t key) {
+            if (key) {
+                const uint32_t pos = atomicAdd(&red[3], 1u);
+                if (pos < (uint32_t)CAP) cand[pos] = key;
+            }
+        });
+        __syncthreads();
+        n_out = min(min(red[3], (uint32_t)CAP), h.k);  // (each depth list holds <= depth keys: red[3] <= 2 x depth = h.k)
+    } else {
+        // ---- top-k of the fused scores over the union (ties: lower ordinal)
+        uint32_t members;
+        uint64_t mx_f;
+        const uint64_t T_f = kth_largest_u64<NT>(each_f, h.k, ks, tid, &members, &mx_f);
+        n_out = min(h.k, members);
+        each_f([&](const uint64_t key) {
+            if (key && key >= T_f) {
+                const uint32_t pos = atomicAdd(&red[3], 1u);
+                if (pos < (uint32_t)kCandCap) cand[pos] = key;
+            }
+        });
+        __syncthreads();
+    }
     rank_and_emit<NT, true>(cand, (int)n_out, (int)h.k, res, tid);
     __syncthreads();
     for (uint32_t i = tid; i < h.k; i += NT) {
@@ -1375,6 +1407,44 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
     if (tid == 0) {
         h.out_n[q] = (int32_t)n_out;
         h.flags[q] = 0;
+    }
+    if constexpr (UNION) {
+        const uint64_t o = (uint64_t)q * h.k;
+        if (u.range && tid == 0) {
+            float* const r = u.range + (uint64_t)q * 4;
+            r[0] = dmax, r[1] = dmin, r[2] = smax, r[3] = smin;
+        }
+        if (!(u.src || u.sparse || u.dense)) return;  // (uniform)
+        for (uint32_t i = n_out + tid; i < h.k; i += NT) {
+            if (u.src) u.src[o + i] = 0;
+            if (u.sparse) u.sparse[o + i] = 0u;
+            if (u.dense) u.dense[o + i] = 0.f;
+        }
+        // every member back to its record: the rank of its fused key in the sorted (descending, unique) keys
+        auto place = [&](const uint64_t key, uint32_t ord, uint32_t sv, uint32_t dv) {
+            if (!key) return;
+            uint32_t lo = 0, hi = n_out;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (res[mid] > key) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo >= n_out) return;  // (cannot happen: every non-zero key was collected)
+            const bool in_s = need_s && sv && comp(sv, ord) >= T_s;
+            const bool in_d = need_d && dv && comp(dv, ord) >= T_d;
+            if (u.src) u.src[o + lo] = (uint8_t)((in_d ? 1u : 0u) | (in_s ? 2u : 0u));
+            if (u.sparse) u.sparse[o + lo] = in_s ? sv : 0u;
+            if (u.dense) u.dense[o + lo] = in_d ? key_to_f32(dv) : 0.f;
+        };
+        if (in_regs) {
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) place(fk[e], ro[e], rs[e], rd[e]);
+        } else {
+            for (uint32_t i = tid; i < n_slots; i += NT) {
+                const uint32_t ord = g_ord[i], sv = g_s[i], dv = g_d[i];
+                place(fused_key(ord, sv, dv), ord, sv, dv);
+            }
+        }
     }
 }
 
@@ -1635,10 +1705,19 @@ static uint32_t tile_quota(uint64_t tile_docs, uint64_t n, uint32_t depth) {
 // Multi-tile indexes (and k > 64 on one tile): per chunk of queries a GEMM launch on the ordinal-permuted passage matrix,
 // hybrid_tiles<MODE 1> over (query, tile) and hybrid_fuse_query over the queries; flagged queries (normally none) are
 // repeated with quota = depth. ms = {candidate kernel, dense GEMM, 0, fusion kernel}.
+// un != null (msr_hybrid_search_union): k = 2 x depth is the row length, hybrid_fuse_query<UNION> keeps the whole union and fills
+// the optional arrays that un names (host pointers, null = not wanted: neither allocated, written nor downloaded).
+struct UnionHost {
+    uint8_t* src;
+    uint32_t* sparse;
+    float* dense;
+    float* range;
+};
+
 static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term,
                                    const int32_t* q_w, const void* q, int nq, int depth, int k, float alpha,
                                    uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord,
-                                   float* out_score, int32_t* out_n, float ms[4]) {
+                                   float* out_score, int32_t* out_n, float ms[4], const UnionHost* un = nullptr) {
     DeviceIndex* d = ix->dev;
     const IndexHeader* h = ix->host.h;
     const uint64_t n = h->n_docs;
@@ -1674,9 +1753,18 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     uint32_t* d_flags = (uint32_t*)dx->take(msr_dense::S_FLAGS, std::max<size_t>(nq, 1) * 4);
     uint32_t* d_qlist = (uint32_t*)dx->take(msr_dense::S_QLIST, std::max<size_t>(nq, 1) * 4);
     bool ok = s.ok && d_rec && d_meta && d_flags && d_qlist;
+    UnionOut uo = {nullptr, nullptr, nullptr, nullptr};
+    const size_t per_union = std::max<size_t>((size_t)nq * k, 1);  // (un: k = 2 x depth)
+    if (un) {
+        if (un->src) ok = (uo.src = (uint8_t*)dx->take(msr_dense::S_USRC, per_union)) != nullptr && ok;
+        if (un->sparse) ok = (uo.sparse = (uint32_t*)dx->take(msr_dense::S_USPARSE, per_union * 4)) != nullptr && ok;
+        if (un->dense) ok = (uo.dense = (float*)dx->take(msr_dense::S_UDENSE, per_union * 4)) != nullptr && ok;
+        if (un->range) ok = (uo.range = (float*)dx->take(msr_dense::S_URANGE, std::max<size_t>(nq, 1) * 16)) != nullptr && ok;
+    }
     int rc = MSR_OK;
     if (!ok) {
-        set_error("device allocation or query upload failed in msr_hybrid_search (%u queries per chunk, %u tiles)", qc, n_tiles);
+        set_error("device allocation or query upload failed in %s (%u queries per chunk, %u tiles)",
+                  un ? "msr_hybrid_search_union" : "msr_hybrid_search", qc, n_tiles);
         rc = MSR_E_NOMEM;
     }
     ha.qlist = nullptr;
@@ -1715,10 +1803,15 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
         }
         if (e) (void)hipEventRecord(e[2], d->stream);
         // (a query's records stay in registers while they fit: 16 per thread)
-        if ((uint64_t)ha.n_tiles * ha.stride <= 256u * 16u)
-            hipLaunchKernelGGL((hybrid_fuse_query<256, 16>), dim3(rows), dim3(256), 0, d->stream, ha, q0);
+        const bool small = (uint64_t)ha.n_tiles * ha.stride <= 256u * 16u;
+        if (un && small)
+            hipLaunchKernelGGL((hybrid_fuse_query<256, 16, true>), dim3(rows), dim3(256), 0, d->stream, ha, q0, uo);
+        else if (un)
+            hipLaunchKernelGGL((hybrid_fuse_query<512, 16, true>), dim3(rows), dim3(512), 0, d->stream, ha, q0, uo);
+        else if (small)
+            hipLaunchKernelGGL((hybrid_fuse_query<256, 16>), dim3(rows), dim3(256), 0, d->stream, ha, q0, uo);
         else
-            hipLaunchKernelGGL((hybrid_fuse_query<512, 16>), dim3(rows), dim3(512), 0, d->stream, ha, q0);
+            hipLaunchKernelGGL((hybrid_fuse_query<512, 16>), dim3(rows), dim3(512), 0, d->stream, ha, q0, uo);
         if (hipGetLastError() != hipSuccess) {
             set_error("hybrid_fuse_query launch failed: %s", hipGetErrorString(hipGetLastError()));
             return MSR_E_HIP;
@@ -1814,6 +1907,14 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
             t_fuse += f;
         }
         rc = hybrid_download(ha, nq, k, out_ord, out_score, out_n);
+        if (rc == MSR_OK && un && nq &&
+            ((un->src && hipMemcpy(un->src, uo.src, (size_t)nq * k, hipMemcpyDeviceToHost) != hipSuccess) ||
+             (un->sparse && hipMemcpy(un->sparse, uo.sparse, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+             (un->dense && hipMemcpy(un->dense, uo.dense, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+             (un->range && hipMemcpy(un->range, uo.range, (size_t)nq * 16, hipMemcpyDeviceToHost) != hipSuccess))) {
+            set_error("download of the union's side arrays failed in msr_hybrid_search_union");
+            rc = MSR_E_HIP;
+        }
     }
     if (ms) {
         ms[0] = t_cand;
@@ -2003,6 +2104,59 @@ int msr_hybrid_search_f32(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, co
     }
     return hybrid_search_impl("msr_hybrid_search_f32", ix, dx, q_ptr, q_term, q_w, q, nq, depth, k, alpha, flags, row2ord,
                               self_ord, out_ord, out_score, out_n, ms);
+}
+
+int msr_hybrid_search_union(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                            const void* q, int q_is_f32, int nq, int depth, float alpha, uint32_t flags,
+                            const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
+                            int32_t* out_n, uint8_t* out_src, uint32_t* out_sparse_u32, float* out_dense, float* out_range,
+                            float ms[4]) {
+    if (!ix || !dx || !row2ord || !out_ord || !out_score || !out_n || nq < 0 || (nq && !q)) {
+        set_error("msr_hybrid_search_union: bad argument");
+        return MSR_E_INVAL;
+    }
+    if ((q_is_f32 != 0) != dx->f32) {
+        if (dx->f32)
+            set_error("msr_hybrid_search_union: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass "
+                      "f32 queries with q_is_f32 = 1, or open an fp16 handle with msr_dense_open");
+        else
+            set_error("msr_hybrid_search_union: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass "
+                      "fp16 queries with q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32");
+        return MSR_E_INVAL;
+    }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound; there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    if (ix->dev->device != dx->device) {
+        set_error("the sparse and the dense index live on different devices");
+        return MSR_E_INVAL;
+    }
+    if (depth < 1 || depth > MSR_KMAX) {
+        set_error("msr_hybrid_search_union: depth must be in [1, %d]", MSR_KMAX);
+        return MSR_E_RANGE;
+    }
+    const IndexHeader* h = ix->host.h;
+    if (dx->n != h->n_docs) {
+        set_error("the dense index holds %llu rows but the sparse index %llu docs", (unsigned long long)dx->n,
+                  (unsigned long long)h->n_docs);
+        return MSR_E_INVAL;
+    }
+    // the handles the candidate path of hybrid_search_impl takes; there is no list-based union
+    const char* why = nullptr;
+    if (ix->term_nshards != 0) why = "a term-range shard handle";
+    else if (ix->shard_ntiles != h->n_tiles) why = "a doc-range shard handle";
+    else if (h->tile_docs != 4096 && h->tile_docs != 8192) why = "a tile size other than 4096 / 8192 docs";
+    else if (h->n_tiles > kMaxGridY) why = "more tiles than one launch holds";
+    else if (!dx->f32 && dx->h % 8 != 0) why = "an fp16 dense dimension that is not a multiple of 8";
+    if (why) {
+        set_error("msr_hybrid_search_union: %s is not supported (tile_docs %u, %u of %u tiles resident): the whole union "
+                  "needs a whole-index handle with 4096- or 8192-doc tiles", why, h->tile_docs, ix->shard_ntiles, h->n_tiles);
+        return MSR_E_INVAL;
+    }
+    const UnionHost un = {out_src, out_sparse_u32, out_dense, out_range};
+    return hybrid_search_multitile(ix, dx, q_ptr, q_term, q_w, q, nq, depth, 2 * depth, alpha, flags, row2ord, self_ord,
+                                   out_ord, out_score, out_n, ms, &un);
 }
 
 }  // extern "C"

@@ -237,3 +237,46 @@ def _hybrid_call(fn, sparse_index, dense_index, q_ptr, q_term, q_w, q, depth, k,
     check(fn(sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w), ptr(q), nq, int(depth), int(k),
              float(alpha), MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so), ptr(ords), ptr(sc), ptr(n), ms))
     return ords, sc, n, dict(sparse=ms[0], dense_gemm=ms[1], dense_select=ms[2], fusion=ms[3])
+
+
+def hybrid_search_union(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, alpha, row2ord, self_ord=None,
+                        drop_df_eq_n=True, with_lists=True):
+    """The whole fused union and both depth lists from ONE call (msr_hybrid_search_union): what the reference's hybrid run
+    writes per query (src/search.py:455-461) — fuse() keeps every doc of either list, src/hybrid.py:32-53 — without a
+    second sparse search or a second GEMM. fp16 or f32 follows dense_index.precision.
+    -> (doc ordinals uint32 [nq, 2*depth] by fused score descending, fused scores float32, n [nq],
+        src uint8 (bit 0: in the dense depth list, bit 1: in the sparse one), exact sparse scores uint32, dense scores
+        float32, score_range float32 [nq, 4] = {dense max, dense min, sparse max, sparse min} of the unfiltered lists,
+        kernel ms per stage); with_lists=False: None for src, the two score arrays and score_range (not downloaded)."""
+    from . import _cabi
+    from ._cabi import MSR_F_DROP_DF_EQ_N
+
+    f32 = getattr(dense_index, "precision", "fp16") == "f32"
+    if f32:
+        q = _as_f32_rows(q_reps, dense_index.dim)
+    else:
+        q = _as_fp16_rows(q_reps, dense_index.dim, dense_index).view(np.uint16)   # (consumed by the synchronous call below)
+    q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
+    nq = len(q_ptr) - 1
+    if q.shape[0] != nq:
+        raise ValueError("sparse and dense query counts differ")
+    row2ord = np.ascontiguousarray(row2ord, dtype=np.uint32)
+    if row2ord.shape != (dense_index.n,):
+        raise ValueError(f"row2ord needs one ordinal per dense row ({dense_index.n}), got shape {row2ord.shape}")
+    so = None if self_ord is None else np.ascontiguousarray(self_ord, dtype=np.int32)
+    if so is not None and so.shape != (nq,):
+        raise ValueError(f"self_ord needs one entry per query ({nq}), got shape {so.shape}")
+    w = 2 * max(int(depth), 0)
+    ords = np.empty((nq, w), dtype=np.uint32)
+    sc = np.empty((nq, w), dtype=np.float32)
+    n = np.zeros(nq, dtype=np.int32)
+    src = su = de = rng = None
+    if with_lists:
+        src, su = np.empty((nq, w), dtype=np.uint8), np.empty((nq, w), dtype=np.uint32)
+        de, rng = np.empty((nq, w), dtype=np.float32), np.empty((nq, 4), dtype=np.float32)
+    ms = (C.c_float * 4)()
+    check(lib().msr_hybrid_search_union(sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w), ptr(q),
+                                        1 if f32 else 0, nq, int(depth), float(alpha),
+                                        MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so), ptr(ords), ptr(sc),
+                                        ptr(n), ptr(src), ptr(su), ptr(de), ptr(rng), ms))
+    return ords, sc, n, src, su, de, rng, dict(sparse=ms[0], dense_gemm=ms[1], dense_select=ms[2], fusion=ms[3])

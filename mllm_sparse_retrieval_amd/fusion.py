@@ -70,6 +70,81 @@ def fuse_statistic(runs, weights):
     return fused
 
 
+_SRC_TYPES = (None, "dense", "sparse", "fuse")  # out_src of msr_hybrid_search_union -> ResultRecord.type
+
+
+def _list_run(qids, names, member, key, scores, lo, hi, empty):
+    """One depth list per query out of the union arrays: the members flagged by `member`, ordered by `key` ascending
+    (a composite of descending score and ascending ordinal), as {'docs': {doc: score}, 'min_score', 'max_score'}."""
+    import numpy as np
+
+    big = np.uint64(0xFFFFFFFFFFFFFFFF)  # (no member's key: the ordinal half stays below 2^32 - 1)
+    order = np.argsort(np.where(member, key, big), axis=1, kind="stable")
+    cnt = member.sum(axis=1)
+    docs = np.take_along_axis(names, order, axis=1)
+    vals = np.take_along_axis(scores, order, axis=1)
+    run = {}
+    for i, qid in enumerate(qids):
+        c = int(cnt[i])
+        v = vals[i, :c]
+        run[qid] = {"docs": dict(zip(docs[i, :c].tolist(), v.tolist() if v.dtype != np.float32 else v)),
+                    "min_score": 0 if empty[i] else lo[i], "max_score": 0 if empty[i] else hi[i]}
+    return run
+
+
+def union_to_runs(qids, docid_table, ords, n, fused, src=None, sparse_u32=None, dense=None, score_range=None):
+    """The arrays of dense.hybrid_search_union -> (sparse_run, dense_run, fusion_run) in the layouts of get_run_dict
+    (src/search.py:66-82) and fuse (src/hybrid.py:32-53): the two lists as {'docs': {doc: score}, 'min_score',
+    'max_score'} with docs best first (score ties: lower ordinal, in both lists) and min / max from score_range, i.e. over
+    the UNFILTERED list as get_run_dict takes them; the fused run as {qid: {doc: score}} best first. Sparse and fused
+    scores are Python floats of the f32 values, dense scores numpy float32, as the other GPU route builds them.
+    docid_table: ordinal -> external id (SparseIndex.docid_table()). Without the four list arrays (a with_lists=False
+    call) the two list runs come back empty and only the fused run is built."""
+    import numpy as np
+
+    ords, n = np.asarray(ords), np.asarray(n)
+    nq, w = ords.shape
+    if n.shape != (nq,) or len(qids) != nq:
+        raise ValueError(f"expected one member count and one query id per row of ords ({nq}), got n of shape {n.shape} "
+                         f"and {len(qids)} ids")
+    live = np.arange(w)[None, :] < n[:, None]
+    table = np.asarray(docid_table, dtype=object)
+    names = table[np.where(live, ords, 0)] if len(table) else np.empty((nq, w), dtype=object)
+    fused_rows = np.asarray(fused, dtype=np.float32)
+    fusion_run = {qid: dict(zip(names[i, :n[i]].tolist(), fused_rows[i, :n[i]].tolist())) for i, qid in enumerate(qids)}
+    if src is None:
+        return {}, {}, fusion_run
+    src = np.asarray(src)
+    o64 = ords.astype(np.uint64)
+    s_u32 = np.asarray(sparse_u32, dtype=np.uint32)
+    d_f32 = np.ascontiguousarray(dense, dtype=np.float32)
+    bits = d_f32.view(np.uint32)
+    d_key = np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.uint64)  # order-preserving
+    rng = np.asarray(score_range, dtype=np.float32)
+    sparse_run = _list_run(qids, names, live & ((src & 2) != 0), ((np.uint64(0xFFFFFFFF) - s_u32.astype(np.uint64)) << np.uint64(32)) | o64,
+                           s_u32.astype(np.float32).astype(np.float64), rng[:, 3].tolist(), rng[:, 2].tolist(),
+                           rng[:, 2] == 0)
+    dense_run = _list_run(qids, names, live & ((src & 1) != 0), ((np.uint64(0xFFFFFFFF) - d_key) << np.uint64(32)) | o64, d_f32,
+                          rng[:, 1], rng[:, 0], np.zeros(nq, dtype=bool) if len(table) else np.ones(nq, dtype=bool))
+    return sparse_run, dense_run, fusion_run
+
+
+def union_to_statistic(qids, docid_table, ords, n, fused, src):
+    """The arrays of dense.hybrid_search_union -> {qid: {doc: ResultRecord}} as fuse_statistic([dense, sparse], ...)
+    returns it (src/hybrid.py:56-90): the fused score and 'dense' / 'sparse' / 'fuse' for where it came from."""
+    import numpy as np
+
+    ords, n, src = np.asarray(ords), np.asarray(n), np.asarray(src)
+    table = np.asarray(docid_table, dtype=object)
+    fused_rows = np.asarray(fused, dtype=np.float32)
+    out = {}
+    for i, qid in enumerate(qids):
+        c = int(n[i])
+        out[qid] = {d: ResultRecord(s, _SRC_TYPES[t & 3]) for d, s, t in
+                    zip(table[ords[i, :c]].tolist(), fused_rows[i, :c].tolist(), src[i, :c].tolist())}
+    return out
+
+
 def write_trec_run(run, file, name="fusion"):
     """src/hybrid.py:20-29: `qid Q0 doc rank score name`, docs by score descending (stable)."""
     with open(file, "w") as f:

@@ -122,7 +122,8 @@ int msr_docid_str(const msr_index* ix, uint32_t ord, const char** s);
  * Queries are CSR: query i owns entries [q_ptr[i], q_ptr[i+1]) of (q_term, q_w). Entries with q_term < 0
  * (out-of-vocabulary) or q_w <= 0 are ignored; duplicate terms add (src/search.py:419-422).
  * Outputs (row-major [nq][k]): doc ordinals, scores as f32 (`hit.score`), optional exact u32 scores,
- * and out_n[i] = number of hits of query i (only docs with score > 0 are hits, so out_n[i] <= k). */
+ * and out_n[i] = number of hits of query i (only docs with score > 0 are hits, so out_n[i] <= k). The f32 score is
+ * (float)u32, round to nearest even; slots past out_n[i] hold ordinal 0xFFFFFFFF and score 0 / 0.f. */
 int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int k,
                    uint32_t flags, uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32,
                    int32_t* out_n);

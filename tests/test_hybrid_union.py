@@ -12,11 +12,14 @@ import numpy as np
 import pytest
 
 from tests import helpers
-from tests.f32_chain import chain_scores, f32_keys
+from tests.f32_chain import f32_keys
+from tests.helpers import check_union as _check_union
+from tests.helpers import union_dense_lists as _dense_lists
+from tests.helpers import union_oracle_runs as _oracle_runs
 
 pytestmark = pytest.mark.gpu
 
-TOL, TIE = 1e-5, 2e-6          # the project's fused-score tolerance and near-tie window (tests/helpers.py)
+TOL, TIE = helpers.UNION_TOL, helpers.UNION_TIE    # the project's fused-score tolerance and near-tie window
 PAD = 0xFFFFFFFF
 
 
@@ -36,85 +39,6 @@ def _rows(rng, n, h, prec, dup_every=0):
     if dup_every and n > dup_every:
         x[dup_every::dup_every] = x[0]  # bit-equal rows: exact dense ties that the depth boundary may cut
     return x
-
-
-def _dense_lists(q, p, depth, prec, tie_key):
-    """Dense top-depth (scores f32 [nq, depth'], rows) with ties to the lower tie_key, and the full score matrix."""
-    if prec == "f32":
-        s = chain_scores(q, p)
-    else:
-        s = q.astype(np.float16).astype(np.float32) @ p.astype(np.float16).astype(np.float32).T
-    keys = f32_keys(s).astype(np.int64)
-    tk = np.broadcast_to(np.asarray(tie_key, np.int64), s.shape)
-    order = np.lexsort((tk, -keys), axis=1)[:, :min(depth, p.shape[0])]
-    return np.take_along_axis(s, order, axis=1), order, s
-
-
-def _oracle_runs(docs, n_terms, ids, qp, qt, qw, sample, depth, remove, qids, d_scores, d_rows):
-    """The two run dicts of the reference's pipeline for the queries in `sample` (dense lists given, best first) and the
-    exact integer sparse scores -> (o_sparse, o_dense, {qid: {doc: int}}, qids of the sample)."""
-    from oracle import oracle
-
-    oix, order = helpers.taat_oracle(docs, n_terms, ids)
-    sorted_ids = [ids[r] for r in order]
-    sample = np.asarray(sample)
-    sel = np.concatenate([np.arange(qp[i], qp[i + 1]) for i in sample])
-    sp = np.concatenate([[0], np.cumsum(qp[sample + 1] - qp[sample])]).astype(np.int64)
-    wo, wsc, wn = oix.search(sp, qt[sel], qw[sel], depth, threads=16)
-    sq = [qids[int(i)] for i in sample]
-    s_docs = [[sorted_ids[int(d)] for d in wo[j, :wn[j]]] for j in range(len(sample))]
-    o_sparse = oracle.get_run_dict(sq, [[float(np.float32(x)) for x in wsc[j, :wn[j]]] for j in range(len(sample))],
-                                   s_docs, remove)
-    o_dense = oracle.get_run_dict(sq, [list(map(float, r)) for r in d_scores],
-                                  np.array([[ids[int(j)] for j in row] for row in d_rows]), remove)
-    exact = {sq[j]: {d: int(x) for d, x in zip(s_docs[j], wsc[j, :wn[j]])} for j in range(len(sample))}
-    return o_sparse, o_dense, exact, sq
-
-
-def _check_union(res, sample, sq, o_sparse, o_dense, exact, alpha, depth, ix, dense_of):
-    """Everything tests 1-3 of the union ask of one result: exact membership and fused order (assert_hybrid_matches at
-    k = 2 x depth plus set equality), the side arrays, the padding, and union_to_runs against the oracle's run dicts.
-    dense_of(j, doc) -> the f32 dense score the call must report for sample query j and that doc."""
-    from mllm_sparse_retrieval_amd import fusion
-    from oracle import oracle
-
-    ords, fs, cnt, src, su, de, rng, _ = res
-    w = 2 * depth
-    assert ords.shape == fs.shape == src.shape == su.shape == de.shape == (len(cnt), w) and rng.shape == (len(cnt), 4)
-    want = oracle.fuse([o_dense, o_sparse], [alpha, 1 - alpha])
-    helpers.assert_hybrid_matches(want, sq, sample, ords, fs, cnt, ix.docid, w, tol=TOL, tie=TIE)
-    stat = fusion.fuse_statistic([o_dense, o_sparse], [alpha, 1 - alpha])
-    bits_of = {"dense": 1, "sparse": 2, "fuse": 3}
-    table = ix.docid_table()
-    for j, i in enumerate(sample):
-        c, qid = int(cnt[i]), sq[j]
-        got_docs = table[ords[i, :c]].tolist()
-        assert set(got_docs) == set(want[qid]) and len(set(got_docs)) == c, qid        # exact membership
-        assert (np.diff(fs[i, :c]) <= 0).all()
-        for r, doc in enumerate(got_docs):
-            b = bits_of[stat[qid][doc].type]
-            assert src[i, r] == b, (qid, doc, int(src[i, r]), b)
-            assert su[i, r] == (exact[qid][doc] if b & 2 else 0), (qid, doc)
-            if b & 1:
-                assert np.float32(de[i, r]).view(np.uint32) == np.float32(dense_of(j, doc)).view(np.uint32), (qid, doc)
-            else:
-                assert de[i, r].view(np.uint32) == 0, (qid, doc)
-        assert (ords[i, c:] == PAD).all() and (fs[i, c:].view(np.uint32) == 0).all()
-        assert (src[i, c:] == 0).all() and (su[i, c:] == 0).all() and (de[i, c:].view(np.uint32) == 0).all()
-        want_rng = [o_dense[qid]["max_score"], o_dense[qid]["min_score"], o_sparse[qid]["max_score"], o_sparse[qid]["min_score"]]
-        assert (rng[i] == np.float32(want_rng)).all(), (qid, rng[i], want_rng)
-    rows = np.asarray(sample)
-    s_run, d_run, f_run = fusion.union_to_runs(sq, table, ords[rows], cnt[rows], fs[rows], src[rows], su[rows], de[rows],
-                                               rng[rows])
-    for got, ref, exact_bits in ((s_run, o_sparse, False), (d_run, o_dense, True)):
-        for qid in sq:
-            assert list(got[qid]["docs"]) == list(ref[qid]["docs"]), qid               # same docs, best first
-            a = np.float32(list(got[qid]["docs"].values()))
-            b = np.float32(list(ref[qid]["docs"].values()))
-            assert (a.view(np.uint32) == b.view(np.uint32)).all() if exact_bits else (a == b).all(), qid
-            assert np.float32(got[qid]["max_score"]) == np.float32(ref[qid]["max_score"]), qid
-            assert np.float32(got[qid]["min_score"]) == np.float32(ref[qid]["min_score"]), qid
-    assert all(set(f_run[qid]) == set(want[qid]) for qid in sq)
 
 
 def _corpus(m, tmp_path, prec, n, tile, h, nq, seed, dup_every, n_terms=2000):

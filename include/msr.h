@@ -128,6 +128,32 @@ int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, c
                    uint32_t flags, uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32,
                    int32_t* out_n);
 
+/* ---- exact ranks of listed docs: "where does this doc stand for this query", at any depth. Stands beside the ranked
+ * lists the reference reads its hits from (src/search.py:86-99) and the recall counting over them (src/metrices.py);
+ * there is NO counterpart call in the reference or in pyserini: a judged doc below the search depth is simply missing
+ * there, so MedR / MeanR / MRR / Recall@k beyond the depth cannot be computed exactly from a run.
+ * Queries are CSR and normalised exactly as by msr_search_csr (q_term < 0 and q_w <= 0 ignored, duplicate terms add,
+ * MSR_F_DROP_DF_EQ_N honoured, the same MSR_E_OVERFLOW / MSR_E_RANGE refusals). The listed docs (targets) are CSR too:
+ * query i owns entries [t_ptr[i], t_ptr[i+1]) of t_ord (doc ordinals; at most MSR_RANK_MAX_TARGETS per query, duplicates
+ * allowed, none is fine). Both outputs are indexed like t_ord. With s(d) the exact u32 score of doc d for the query:
+ *     out_score_u32 = s(t)
+ *     out_rank      = 0 when s(t) == 0 (not a hit: no search returns it) or t == self_ord[i],
+ *                     else 1 + #{ d != self_ord[i] : s(d) > s(t) or (s(d) == s(t) and d < t) }
+ * i.e. the search path's key order (score descending, lower ordinal wins). self_ord (nullable; entries may be -1) names
+ * the doc remove_query drops (src/search.py:72-74). With self_ord NULL and any k <= MSR_KMAX, t is in row i of
+ * msr_search_csr(..., k) exactly when 1 <= rank <= k, at column rank - 1 with the same u32 score.
+ * ms (nullable) = HIP-event times of {the gather launch(es): scores of the listed docs, tiles without one are not
+ * touched; the count launch(es) over every (tile, query) plus the reduction}.
+ * Only a whole-index handle is served: a doc-range or term-range shard handle is refused with MSR_E_INVAL (a rank
+ * counts over every doc and needs every term). Argument errors are reported before the device is looked at:
+ * MSR_E_INVAL for a null ix / q_ptr / t_ptr / output, nq < 0, a t_ptr that does not start at 0 or decreases;
+ * MSR_E_RANGE for an ordinal or a self_ord entry >= n_docs and for more than MSR_RANK_MAX_TARGETS targets in one query;
+ * then MSR_E_NODEVICE on a handle opened with device < 0. nq == 0 or no target at all returns MSR_OK without a launch. */
+#define MSR_RANK_MAX_TARGETS 64 /* listed docs per query */
+int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, uint32_t flags,
+                  const int64_t* t_ptr, const uint32_t* t_ord, const int32_t* self_ord, uint32_t* out_rank,
+                  uint32_t* out_score_u32, float ms[2]);
+
 /* Where the calling thread's last msr_search_csr spent its time, in microseconds: {query normalisation + device buffers
  * + upload enqueued, kernels enqueued, wait for the stream, download + copy out, release, the whole call, 0, 0}. Slots 6
  * and 7 (once HIP-event spans of the kernels) stay in the ABI and are always 0: the call records no events. The reference

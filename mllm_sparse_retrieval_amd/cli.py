@@ -4,6 +4,7 @@
     python -m mllm_sparse_retrieval_amd index  --input out/ [--index out/index] --threads 16       (sparse_index.sh)
     python -m mllm_sparse_retrieval_amd search --sparse_index out/ --depth 10 --query_type text \\
            --dataset_name flickr --queries out/query.tsv --qrels out/qrels.csv --save_dir runs/   (search_sparse.sh)
+           [--ranks: exact rank of every judged doc at any depth -> recall / MRR / MedR / MeanR, sparse.ranks.tsv]
     python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
 
@@ -122,6 +123,14 @@ def _check_search_args(a):
         sys.exit("search: give --sparse_index (sparse or hybrid search) and/or --passage_reps (dense search)")
     if a.sparse_index is None and not 1 <= a.depth <= MSR_KMAX:
         sys.exit(f"search: dense-only --depth must be in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth})")
+    if getattr(a, "ranks", False):
+        if a.passage_reps is not None:
+            sys.exit("search: --ranks is the sparse-only route (exact ranks come from the sparse index alone): drop "
+                     "--passage_reps")
+        if not a.qrels:
+            sys.exit("search: --ranks ranks every query's judged docs and needs --qrels")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("search: --ranks runs in one process (no launcher, WORLD_SIZE = 1)")
     if getattr(a, "hybrid_f32", False):
         if a.use_gpu:
             sys.exit("search: --hybrid_f32 and --use_gpu contradict each other (--use_gpu is the reference's fp16 GPU "
@@ -273,6 +282,7 @@ def _cmd_search(a):
                                 done |= mine
                         for p in parts:
                             os.remove(p)
+    ds = None
     if a.qrels:
         ds = CrossModalQrels(a.qrels, a.dataset_name)
         m = RecallMetrics(ds, dense_run, sparse_run, fusion_run, p_lookup or [], qids, args,
@@ -280,10 +290,43 @@ def _cmd_search(a):
         m.sort_and_count()
         m.all_gather_object()
         m.print_recall()
+    if getattr(a, "ranks", False):
+        _report_exact_ranks(a, searcher, ds, qids, texts)
     if searcher is not None:
         searcher.close()
     if world > 1:
         dist.barrier()
+
+
+def _report_exact_ranks(a, searcher, ds, qids, texts):
+    """search --ranks: the exact rank of every query's judged docs from ONE rank_docs call over the whole query file
+    (no depth limit, so MRR / MedR / MeanR are exact), --remove_query honoured as get_run_dict does. Prints one line and,
+    with --save_dir, writes sparse.ranks.tsv: qid, docid, rank, score per (query, target); rank 0 = not a hit or the
+    query's own doc, rank -1 = the index does not hold that doc id."""
+    import numpy as np
+
+    from .ranks import rank_metrics
+
+    targets = []
+    for qid in qids:
+        t = ds.get_target(qid, a.query_type)
+        targets.append([str(x) for x in t] if isinstance(t, list) else [str(t)])
+    res = searcher.batch_rank(texts, qids, targets, remove_query=a.remove_query)
+    ranks, t_ptr, missing = [], [0], 0
+    for qid, row in res.items():
+        ranks.extend(r for _, r, _ in row if r is not None)
+        missing += sum(1 for _, r, _ in row if r is None)
+        t_ptr.append(len(ranks))
+    m = rank_metrics(np.asarray(ranks, np.int64), np.asarray(t_ptr, np.int64), searcher.num_docs)
+    rc = m["recall"]
+    print("Sparse exact ranks: r@1 {}, r@5 {}, r@10 {}, r@100 {}, r@200 {}, mrr {}, medr {}, meanr {}, unranked {}, "
+          "missing {}".format(rc[1], rc[5], rc[10], rc[100], rc[200], m["mrr"], m["medr"], m["meanr"], m["n_unranked"],
+                              missing))
+    if a.save_dir:
+        with open(os.path.join(a.save_dir, "sparse.ranks.tsv"), "w") as f:
+            for qid, row in res.items():
+                for d, r, sc in row:
+                    f.write(f"{qid}\t{d}\t{-1 if r is None else r}\t{0 if sc is None else sc}\n")
 
 
 def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids):
@@ -458,6 +501,10 @@ def main(argv=None):
                         "handle; --depth <= 1024, not with --host_fusion, --fusion_k is ignored")
     s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs (with or without --fusion_union; "
                                                                    "the fused run then feeds the recall report only: fusion.trec is written beside a dense run)")
+    s.add_argument("--ranks", action="store_true",
+                   help="sparse search: after the search, the EXACT rank (no depth limit) of every query's --qrels docs "
+                        "from one msr_rank_docs call; prints recall, MRR, MedR, MeanR and writes sparse.ranks.tsv under "
+                        "--save_dir; honours --remove_query; not with --passage_reps or under a launcher")
     s.add_argument("--compat-denominator", "--compat_denominator", dest="compat_denominator", action="store_true",
                    help="multi-rank: keep the sampler's padded repeats and divide by len(shard) * world like the reference")
     s.set_defaults(fn=_cmd_search)

@@ -11,6 +11,7 @@
 #include <chrono>
 
 #include "msr_kernels.hpp"
+#include "msr_rank.hpp"
 
 namespace msr {
 
@@ -80,6 +81,51 @@ int launch_merge(hipStream_t st, const MergeArgs& a) {
     else
         hipLaunchKernelGGL((merge_lists<256>), dim3(a.nq), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
+    return MSR_OK;
+}
+
+// The rank kernels (msr_rank.hpp) at the accumulation's launch shapes: the <tile, threads, chunk loads per bank, min
+// waves/SIMD of the k <= 512 instance> columns of launch_score's table, the light instance chosen by the same rule.
+// count = false: rank_gather_tiles over pairs [0, n_pairs) of a.pairs (1-D grid);
+// count = true:  rank_count_tiles over queries [a0.s.q0, a0.s.q0 + a0.s.qn) x shard-local tiles [0, t_end).
+constexpr uint32_t kRankMaxGridX = 1u << 30;  // pairs per gather launch (HIP grid limit in x: 2^31 - 1)
+static int launch_rank(hipStream_t st, uint32_t tile_docs, bool count, uint32_t n_pairs, uint32_t t_end, const RankArgs& a0) {
+    const uint32_t n_outer = count ? t_end : n_pairs, step = count ? kMaxGridY : kRankMaxGridX;
+    if (n_outer == 0 || (count && a0.s.qn == 0)) return MSR_OK;
+    for (uint32_t o0 = 0; o0 < n_outer; o0 += step) {
+        RankArgs a = a0;
+        const uint32_t n = std::min<uint32_t>(step, n_outer - o0);
+        dim3 grid(n);
+        if (count) {
+            a.s.tl0 = o0;
+            grid = dim3(a.s.qn, n);
+        } else {
+            a.pairs = a0.pairs + o0;
+        }
+        const bool light = a.s.light != 0;
+        switch (tile_docs) {
+#define MSR_RANK_LAUNCH(T, N, UU, W)                                                                               \
+    if (count && light)                                                                                            \
+        hipLaunchKernelGGL((rank_count_tiles<T, N, UU, W, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a);    \
+    else if (count)                                                                                                \
+        hipLaunchKernelGGL((rank_count_tiles<T, N, UU, W, false>), grid, dim3(N), 0, st, a);                       \
+    else if (light)                                                                                                \
+        hipLaunchKernelGGL((rank_gather_tiles<T, N, UU, W, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a);   \
+    else                                                                                                           \
+        hipLaunchKernelGGL((rank_gather_tiles<T, N, UU, W, false>), grid, dim3(N), 0, st, a);                      \
+    break;
+            case 32768: MSR_RANK_LAUNCH(32768, 1024, 8, 4)
+            case 16384: MSR_RANK_LAUNCH(16384, 512, 8, 4)
+            case 12288: MSR_RANK_LAUNCH(12288, 512, 4, 4)
+            case 8192: MSR_RANK_LAUNCH(8192, 512, 4, 8)
+            case 4096: MSR_RANK_LAUNCH(4096, 256, 4, 6)
+#undef MSR_RANK_LAUNCH
+            default:
+                set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
+                return MSR_E_RANGE;
+        }
+        HIP_TRY(hipGetLastError());
+    }
     return MSR_OK;
 }
 
@@ -976,6 +1022,203 @@ int msr_search_laps(double out_us[8]) {
     }
     memcpy(out_us, g_laps, sizeof(g_laps));
     return MSR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ exact ranks
+// Queries of one count pass: the [tile][entry] partial counts of a pass are device scratch (tiles x entries of the pass
+// x 4 bytes, at most MSR_RANK_MAX_TARGETS entries per query), so a big batch is ranked kRankPassQueries queries at a
+// time. The gather phase is not split: it writes one u32 per listed doc.
+constexpr int kRankPassQueries = 32768;
+
+int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, uint32_t flags,
+                  const int64_t* t_ptr, const uint32_t* t_ord, const int32_t* self_ord, uint32_t* out_rank,
+                  uint32_t* out_score_u32, float ms[2]) {
+    // ---- argument checks: no device needed
+    if (!ix || !q_ptr || !t_ptr || !out_rank || !out_score_u32 || nq < 0) {
+        set_error("msr_rank_docs: bad argument");
+        return MSR_E_INVAL;
+    }
+    if (t_ptr[0] != 0) {
+        set_error("msr_rank_docs: t_ptr must start at 0");
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i)
+        if (t_ptr[i + 1] < t_ptr[i]) {
+            set_error("msr_rank_docs: t_ptr decreases at query %d", i);
+            return MSR_E_INVAL;
+        }
+    const int64_t n_ent64 = t_ptr[nq];
+    if (n_ent64 > 0 && !t_ord) {
+        set_error("msr_rank_docs: null t_ord");
+        return MSR_E_INVAL;
+    }
+    const IndexHeader* h = ix->host.h;
+    if (ix->term_nshards > 0 || ix->shard_ntiles != h->n_tiles) {
+        set_error("msr_rank_docs: a rank counts over every doc and every term; this handle is a %s shard (open the whole "
+                  "index with msr_index_open)", ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i) {
+        if (t_ptr[i + 1] - t_ptr[i] > MSR_RANK_MAX_TARGETS) {
+            set_error("msr_rank_docs: query %d lists %lld docs (at most MSR_RANK_MAX_TARGETS = %d)", i,
+                      (long long)(t_ptr[i + 1] - t_ptr[i]), MSR_RANK_MAX_TARGETS);
+            return MSR_E_RANGE;
+        }
+        if (self_ord && self_ord[i] >= 0 && (uint64_t)self_ord[i] >= h->n_docs) {
+            set_error("msr_rank_docs: self_ord[%d] = %d is outside the index (%llu docs)", i, self_ord[i],
+                      (unsigned long long)h->n_docs);
+            return MSR_E_RANGE;
+        }
+    }
+    for (int64_t e = 0; e < n_ent64; ++e)
+        if ((uint64_t)t_ord[e] >= h->n_docs) {
+            set_error("msr_rank_docs: ordinal %u (entry %lld) is outside the index (%llu docs)", t_ord[e], (long long)e,
+                      (unsigned long long)h->n_docs);
+            return MSR_E_RANGE;
+        }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (nq == 0 || n_ent64 == 0) return MSR_OK;
+    if ((uint64_t)n_ent64 + (uint64_t)nq > 0xFFFFFFF0ull) {
+        set_error("msr_rank_docs: too many listed docs");
+        return MSR_E_RANGE;
+    }
+    const uint32_t n_ent = (uint32_t)n_ent64;
+    DeviceIndex* d = ix->dev;
+    // ---- the queries, normalised and uploaded exactly as for a search (refusals included)
+    msr_batch* b = nullptr;
+    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
+    if (rc != MSR_OK) return rc;
+    // ---- (query, tile) pairs that hold a listed doc or the query's self doc, tile-major; the docs of a pair
+    const uint32_t tile = h->tile_docs, n_tiles = h->n_tiles;
+    struct Item {
+        uint32_t tile, q, slot, local;
+    };
+    std::vector<Item> its;
+    its.reserve((size_t)n_ent + (size_t)nq);
+    for (int i = 0; i < nq; ++i) {
+        for (int64_t e = t_ptr[i]; e < t_ptr[i + 1]; ++e)
+            its.push_back({t_ord[e] / tile, (uint32_t)i, (uint32_t)e, t_ord[e] % tile});
+        if (self_ord && self_ord[i] >= 0)
+            its.push_back({(uint32_t)self_ord[i] / tile, (uint32_t)i, n_ent + (uint32_t)i, (uint32_t)self_ord[i] % tile});
+    }
+    std::stable_sort(its.begin(), its.end(), [](const Item& x, const Item& y) { return x.tile != y.tile ? x.tile < y.tile : x.q < y.q; });
+    // one upload block: t_ptr | t_ord | entry -> query | self | pairs (uint4) | items (uint2)
+    auto al = [](size_t n) { return (n + 63) / 64 * 64; };
+    std::vector<uint32_t> pairs;
+    pairs.reserve(its.size() * 4);
+    for (size_t i = 0; i < its.size(); ++i) {
+        if (i == 0 || its[i].tile != its[i - 1].tile || its[i].q != its[i - 1].q) {
+            const uint32_t row[4] = {its[i].q, its[i].tile, (uint32_t)i, 0u};
+            pairs.insert(pairs.end(), row, row + 4);
+        }
+        ++pairs[pairs.size() - 1];
+    }
+    const uint32_t n_pairs = (uint32_t)(pairs.size() / 4);
+    const size_t o_tp = 0, o_to = o_tp + al((size_t)nq + 1), o_eq = o_to + al(n_ent), o_self = o_eq + al(n_ent),
+                 o_pairs = o_self + al((size_t)nq), o_items = o_pairs + al(pairs.size()), in_words = o_items + al(its.size() * 2);
+    std::vector<uint32_t> blk(in_words, 0u);
+    for (int i = 0; i <= nq; ++i) blk[o_tp + (size_t)i] = (uint32_t)t_ptr[i];
+    memcpy(blk.data() + o_to, t_ord, (size_t)n_ent * 4);
+    for (int i = 0; i < nq; ++i) {
+        for (int64_t e = t_ptr[i]; e < t_ptr[i + 1]; ++e) blk[o_eq + (size_t)e] = (uint32_t)i;
+        blk[o_self + (size_t)i] = (self_ord && self_ord[i] >= 0) ? (uint32_t)self_ord[i] : kRankNoSelf;
+    }
+    memcpy(blk.data() + o_pairs, pairs.data(), pairs.size() * 4);
+    for (size_t i = 0; i < its.size(); ++i) {
+        blk[o_items + 2 * i] = its[i].slot;
+        blk[o_items + 2 * i + 1] = its[i].local;
+    }
+    // passes of the count phase and the scratch of the largest one
+    uint32_t max_pe = 0;
+    for (int q0 = 0; q0 < nq; q0 += kRankPassQueries)
+        max_pe = std::max<uint32_t>(max_pe, (uint32_t)(t_ptr[std::min(nq, q0 + kRankPassQueries)] - t_ptr[q0]));
+    const size_t in_bytes = in_words * 4, sc_bytes = ((size_t)n_ent + (size_t)nq) * 4, rk_bytes = (size_t)n_ent * 4,
+                 part_bytes = std::max<size_t>((size_t)n_tiles * max_pe, 1) * 4;
+    uint32_t* d_in = (uint32_t*)d->pool.alloc(in_bytes);
+    uint32_t* d_sc = (uint32_t*)d->pool.alloc(sc_bytes);
+    uint32_t* d_rk = (uint32_t*)d->pool.alloc(rk_bytes);
+    uint32_t* d_part = (uint32_t*)d->pool.alloc(part_bytes);
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    auto done = [&](int r) {
+        if (r != MSR_OK) (void)hipStreamSynchronize(d->stream);  // nothing in flight may still use the scratch
+        d->pool.release(d_in, in_bytes);
+        d->pool.release(d_sc, sc_bytes);
+        d->pool.release(d_rk, rk_bytes);
+        d->pool.release(d_part, part_bytes);
+        for (hipEvent_t e : ev) {
+            if (!e) continue;
+            if (d->spare_events.size() < 64)
+                d->spare_events.push_back(e);
+            else
+                (void)hipEventDestroy(e);
+        }
+        batch_free(b);
+        return r;
+    };
+    if (!d_in || !d_sc || !d_rk || !d_part) {
+        set_error("msr_rank_docs: device allocation failed (%zu bytes of per-tile counts)", part_bytes);
+        return done(MSR_E_NOMEM);
+    }
+    auto try_hip = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return true;
+        set_error("msr_rank_docs: %s failed: %s", what, hipGetErrorString(e));
+        return false;
+    };
+    if (!try_hip(hipMemcpy(d_in, blk.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return done(MSR_E_HIP);
+    for (int i = 0; ms && i < 3; ++i) {
+        if (!d->spare_events.empty()) {
+            ev[i] = d->spare_events.back();
+            d->spare_events.pop_back();
+        } else if (!try_hip(hipEventCreate(&ev[i]), "hipEventCreate")) {
+            return done(MSR_E_HIP);
+        }
+    }
+    RankArgs ra;
+    fill_score_args(ra.s, b, 1);
+    ra.s.light = b->max_sparse_terms <= 64 ? 1u : 0u;
+    ra.s.part = nullptr;
+    ra.pairs = reinterpret_cast<const uint4*>(d_in + o_pairs);
+    ra.items = reinterpret_cast<const uint2*>(d_in + o_items);
+    ra.score = d_sc;
+    ra.t_ptr = d_in + o_tp;
+    ra.t_ord = d_in + o_to;
+    ra.e_query = d_in + o_eq;
+    ra.self = d_in + o_self;
+    ra.partial = d_part;
+    ra.out_rank = d_rk;
+    ra.n_entries = n_ent;
+    ra.e0 = 0;
+    ra.pe = 0;
+    ra.n_tiles = n_tiles;
+    if (ms && !try_hip(hipEventRecord(ev[0], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    rc = launch_rank(d->stream, tile, false, n_pairs, 0, ra);
+    if (rc != MSR_OK) return done(rc);
+    if (ms && !try_hip(hipEventRecord(ev[1], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    for (int q0 = 0; q0 < nq; q0 += kRankPassQueries) {
+        const int q1 = std::min(nq, q0 + kRankPassQueries);
+        ra.s.q0 = (uint32_t)q0;
+        ra.s.qn = (uint32_t)(q1 - q0);
+        ra.e0 = (uint32_t)t_ptr[q0];
+        ra.pe = (uint32_t)(t_ptr[q1] - t_ptr[q0]);
+        if (ra.pe == 0) continue;
+        rc = launch_rank(d->stream, tile, true, 0, n_tiles, ra);
+        if (rc != MSR_OK) return done(rc);
+        hipLaunchKernelGGL(rank_reduce, dim3((ra.pe + 255) / 256), dim3(256), 0, d->stream, ra);
+        if (!try_hip(hipGetLastError(), "rank_reduce")) return done(MSR_E_HIP);
+    }
+    if (ms && !try_hip(hipEventRecord(ev[2], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    if (!try_hip(hipStreamSynchronize(d->stream), "the rank kernels")) return done(MSR_E_HIP);
+    if (!try_hip(hipMemcpy(out_rank, d_rk, rk_bytes, hipMemcpyDeviceToHost), "download") ||
+        !try_hip(hipMemcpy(out_score_u32, d_sc, (size_t)n_ent * 4, hipMemcpyDeviceToHost), "download"))
+        return done(MSR_E_HIP);
+    if (ms && (!try_hip(hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
+               !try_hip(hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
+        return done(MSR_E_HIP);
+    return done(MSR_OK);
 }
 
 // ------------------------------------------------------------------------------------------------ merge of host lists

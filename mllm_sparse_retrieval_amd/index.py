@@ -201,6 +201,30 @@ class SparseIndex:
                                    ptr(su), ptr(n)))
         return ords, sc, su, n
 
+    def rank_docs(self, q_ptr, q_term, q_w, t_ptr, t_ord, drop_df_eq_n=True, self_ord=None, with_ms=False):
+        """Exact ranks of listed docs (msr_rank_docs): query i lists the ordinals t_ord[t_ptr[i]:t_ptr[i + 1]] (at most
+        MSR_RANK_MAX_TARGETS). Returns (ranks uint32, exact scores uint32), both indexed like t_ord: rank 0 = not a hit
+        (score 0) or the query's own doc (self_ord[i], -1 for none), else 1 + the docs that beat it (score descending,
+        lower ordinal wins) — at any depth, not only within MSR_KMAX. with_ms=True appends the HIP-event times
+        (gather ms, count + reduction ms)."""
+        q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
+        nq = len(q_ptr) - 1
+        t_ptr = np.ascontiguousarray(t_ptr, dtype=np.int64)
+        t_ord = np.ascontiguousarray(t_ord, dtype=np.uint32)
+        if t_ptr.ndim != 1 or len(t_ptr) != nq + 1 or t_ord.ndim != 1 or int(t_ptr[-1]) != len(t_ord):
+            raise ValueError("malformed CSR target arrays")
+        if self_ord is not None:
+            self_ord = np.ascontiguousarray(self_ord, dtype=np.int32)
+            if self_ord.shape != (nq,):
+                raise ValueError("self_ord needs one entry per query")
+        ranks = np.zeros(len(t_ord), dtype=np.uint32)
+        scores = np.zeros(len(t_ord), dtype=np.uint32)
+        ms = (C.c_float * 2)()
+        check(lib().msr_rank_docs(self._h, ptr(q_ptr), ptr(q_term), ptr(q_w), nq, MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0,
+                                  ptr(t_ptr), ptr(t_ord), ptr(self_ord), ptr(ranks), ptr(scores),
+                                  C.cast(ms, C.c_void_p) if with_ms else None))
+        return (ranks, scores, (float(ms[0]), float(ms[1]))) if with_ms else (ranks, scores)
+
     def search_text(self, queries, k, drop_df_eq_n=True):
         """Query strings (tokens repeated `weight` times, src/search.py:419-422) -> the same outputs as search_csr;
         tokenisation, counting and dictionary lookup run in C inside the call."""

@@ -106,3 +106,45 @@ class LuceneImpactSearcher:
             row = score_rows[i]
             out[qid] = [Hit(ids[j], row[j]) for j in range(cnt)]
         return out
+
+    def batch_rank(self, queries, qids, targets, remove_query=False):
+        """Exact rank and score of named docs: targets[i] lists external doc ids for queries[i]. Returns
+        {qid: [(docid, rank, score), ...]} in the given order; rank 0 = not a hit (score 0) or, with remove_query, the
+        query's own doc; an id the index does not hold comes back as (docid, None, None). No pyserini counterpart: a
+        hit list stops at its depth (src/search.py:86-99), these ranks do not (SparseIndex.rank_docs)."""
+        if not (len(queries) == len(qids) == len(targets)):
+            raise ValueError("queries, qids and targets differ in length")
+        table = self.index.docid_table()
+        if getattr(self, "_ord_of", None) is None:
+            self._ord_of = {d: o for o, d in enumerate(table.tolist())}
+        ord_of = self._ord_of
+        if self.min_idf > 0:  # as in batch_search: the idf filter on the host
+            q_ptr, term_ids, ws = self._encode(queries)
+            df = self.index.df(term_ids).astype(np.float64)
+            with np.errstate(divide="ignore"):
+                idf = np.log(self.index.n_docs / np.maximum(df, 1e-300))
+            ws = np.where((df > 0) & (idf > self.min_idf), ws, 0).astype(np.int32)
+            drop = True if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        else:
+            q_ptr, term_ids, ws = self.index.encode_queries(queries)
+            drop = self.min_idf >= 0 if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        t_ptr, t_ord = [0], []
+        for tg in targets:
+            t_ord.extend(ord_of[str(d)] for d in tg if str(d) in ord_of)
+            t_ptr.append(len(t_ord))
+        self_ord = np.asarray([ord_of.get(str(x), -1) for x in qids], dtype=np.int32) if remove_query else None
+        ranks, scores = self.index.rank_docs(q_ptr, term_ids, ws, np.asarray(t_ptr, np.int64), np.asarray(t_ord, np.uint32),
+                                             drop_df_eq_n=drop, self_ord=self_ord)
+        ranks, scores = ranks.tolist(), scores.tolist()
+        out = {}
+        for i, qid in enumerate(qids):
+            e = t_ptr[i]
+            row = []
+            for d in targets[i]:
+                if str(d) in ord_of:
+                    row.append((d, ranks[e], scores[e]))
+                    e += 1
+                else:
+                    row.append((d, None, None))
+            out[qid] = row
+        return out

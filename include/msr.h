@@ -154,6 +154,35 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
                   const int64_t* t_ptr, const uint32_t* t_ord, const int32_t* self_ord, uint32_t* out_rank,
                   uint32_t* out_score_u32, float ms[2]);
 
+/* ---- explain listed docs: "WHY does this doc score what it scores", the stored doc weight of every query term for
+ * listed (query, doc) pairs. Counterpart: Lucene's IndexSearcher.explain(), which the reference never calls (none in
+ * src/search.py; its src/sparse_statistic.py / src/score_statistic.py re-read the encoder output instead). The index is
+ * tile-major inverted, there is no forward index: this call reads the addends out of the segments and the dense head on
+ * the device, with kernels of its own that share no code with the accumulation of the search / rank path.
+ * Queries and listed docs (targets) are CSR exactly as for msr_rank_docs (same query normalisation, same
+ * MSR_E_OVERFLOW / MSR_E_RANGE refusals, at most MSR_EXPLAIN_MAX_TARGETS targets per query, duplicates allowed, none is
+ * fine). out_doc_w is ragged: target entry e of query i(e) owns len_i = q_ptr[i+1] - q_ptr[i] consecutive slots from
+ *     x_off(e) = sum over e' < e of len_i(e'),
+ * and slot j of entry e belongs to input entry q_ptr[i] + j of the query (term tau, weight omega), listed doc t:
+ *     out_doc_w[x_off(e) + j] = w(tau, t), the stored weight of tau in t, when the entry counts,
+ *                               0 when t lacks tau or the entry does not count.
+ * An entry counts when tau >= 0, omega > 0 and it is not dropped by MSR_F_DROP_DF_EQ_N; a repeated term gets the same
+ * weight in each of its slots (duplicates add). out_cap = number of u32 the caller allocated, at least the sum of
+ * len_i(e) over all target entries. IDENTITY: for every entry e,
+ *     sum over j of max(omega_j, 0) * out_doc_w[x_off(e) + j]  ==  out_score_u32[e] of msr_rank_docs on the same inputs.
+ * ms (nullable) = HIP-event time of the explain work on the stream {zeroing the output + the explain launch(es)}.
+ * Only a whole-index handle is served (doc-range and term-range shard handles: MSR_E_INVAL); all five tile sizes, with
+ * or without a dense head. Argument errors are reported before the device is looked at: MSR_E_INVAL for a null ix /
+ * q_ptr / t_ptr / output (or q_term / q_w / t_ord with entries to read), nq < 0, a q_ptr that is negative or decreases,
+ * a t_ptr that does not start at 0 or decreases, an out_cap below the sum above; MSR_E_RANGE for an ordinal >= n_docs
+ * and for more than MSR_EXPLAIN_MAX_TARGETS targets in one query; then MSR_E_NODEVICE on a handle opened with
+ * device < 0. nq == 0, no target at all or only zero-length queries return MSR_OK without a launch. There is no CPU
+ * path. */
+#define MSR_EXPLAIN_MAX_TARGETS 64 /* listed docs per query */
+int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq,
+                     uint32_t flags, const int64_t* t_ptr, const uint32_t* t_ord, uint32_t* out_doc_w, int64_t out_cap,
+                     float ms[1]);
+
 /* Where the calling thread's last msr_search_csr spent its time, in microseconds: {query normalisation + device buffers
  * + upload enqueued, kernels enqueued, wait for the stream, download + copy out, release, the whole call, 0, 0}. Slots 6
  * and 7 (once HIP-event spans of the kernels) stay in the ABI and are always 0: the call records no events. The reference

@@ -17,6 +17,7 @@ MSR_F_DROP_DF_EQ_N = 1
 MSR_KMAX = 1024
 MSR_UNION_MAX = 2 * MSR_KMAX
 MSR_RANK_MAX_TARGETS = 64
+MSR_EXPLAIN_MAX_TARGETS = 64
 MSR_COMM_ID_BYTES = 128
 
 _ERR_NAMES = {
@@ -61,6 +62,7 @@ SYMBOLS = [
     ("msr_docid_str", _I, [_VP, _U32, C.POINTER(_CP)]),
     ("msr_search_csr", _I, [_VP, _VP, _VP, _VP, _I, _I, _U32, _VP, _VP, _VP, _VP]),
     ("msr_rank_docs", _I, [_VP, _VP, _VP, _VP, _I, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("msr_explain_docs", _I, [_VP, _VP, _VP, _VP, _I, _U32, _VP, _VP, _VP, C.c_int64, _VP]),
     ("msr_search_laps", _I, [_VP]),
     ("msr_search_text", _I, [_VP, _VP, _I, _I, _U32, _VP, _VP, _VP, _VP]),
     ("msr_encode_queries", _I, [_VP, _VP, _I, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),

@@ -5,6 +5,7 @@
     python -m mllm_sparse_retrieval_amd search --sparse_index out/ --depth 10 --query_type text \\
            --dataset_name flickr --queries out/query.tsv --qrels out/qrels.csv --save_dir runs/   (search_sparse.sh)
            [--ranks: exact rank of every judged doc at any depth -> recall / MRR / MedR / MeanR, sparse.ranks.tsv]
+           [--explain N: per-token query weight x doc weight of the first N hits and the judged docs, sparse.explain.tsv]
     python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
 
@@ -131,6 +132,17 @@ def _check_search_args(a):
             sys.exit("search: --ranks ranks every query's judged docs and needs --qrels")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("search: --ranks runs in one process (no launcher, WORLD_SIZE = 1)")
+    if getattr(a, "explain", None) is not None:
+        from ._cabi import MSR_EXPLAIN_MAX_TARGETS
+
+        if a.passage_reps is not None:
+            sys.exit("search: --explain is the sparse-only route (the doc weights come from the sparse index alone): drop "
+                     "--passage_reps")
+        if not 1 <= a.explain <= MSR_EXPLAIN_MAX_TARGETS:
+            sys.exit(f"search: --explain N needs 1 <= N <= MSR_EXPLAIN_MAX_TARGETS = {MSR_EXPLAIN_MAX_TARGETS} "
+                     f"(got {a.explain})")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("search: --explain runs in one process (no launcher, WORLD_SIZE = 1)")
     if getattr(a, "hybrid_f32", False):
         if a.use_gpu:
             sys.exit("search: --hybrid_f32 and --use_gpu contradict each other (--use_gpu is the reference's fp16 GPU "
@@ -292,6 +304,8 @@ def _cmd_search(a):
         m.print_recall()
     if getattr(a, "ranks", False):
         _report_exact_ranks(a, searcher, ds, qids, texts)
+    if getattr(a, "explain", None) is not None:
+        _report_explain(a, searcher, ds, qids, texts, sparse_run)
     if searcher is not None:
         searcher.close()
     if world > 1:
@@ -327,6 +341,43 @@ def _report_exact_ranks(a, searcher, ds, qids, texts):
             for qid, row in res.items():
                 for d, r, sc in row:
                     f.write(f"{qid}\t{d}\t{-1 if r is None else r}\t{0 if sc is None else sc}\n")
+
+
+def _report_explain(a, searcher, ds, qids, texts, sparse_run):
+    """search --explain N: the per-token addends of the first N hits of every query (after --remove_query's filter) and,
+    with --qrels, of its judged docs as well (deduplicated), from ONE explain_docs call over the whole query file.
+    Prints one line and, with --save_dir, writes sparse.explain.tsv (explain.tsv_lines: qid, docid, position, judged,
+    score, token, q_w, d_w, contribution; one line per matched token)."""
+    from ._cabi import MSR_EXPLAIN_MAX_TARGETS
+    from .explain import write_tsv
+
+    listed, hits_of, judged_of = [], [], []
+    for qid in qids:
+        hits = list(sparse_run[qid]["docs"])  # in rank order (get_run_dict keeps the hit order)
+        docs = hits[:a.explain]
+        judged = []
+        if ds is not None:
+            t = ds.get_target(qid, a.query_type)
+            judged = [str(x) for x in t] if isinstance(t, list) else [str(t)]
+            docs += [d for d in dict.fromkeys(judged) if d not in docs]
+        if len(docs) > MSR_EXPLAIN_MAX_TARGETS:
+            sys.exit(f"search: --explain: query {qid} would list {len(docs)} docs ({a.explain} hits + its judged docs), "
+                     f"at most MSR_EXPLAIN_MAX_TARGETS = {MSR_EXPLAIN_MAX_TARGETS}: lower --explain")
+        listed.append(docs)
+        hits_of.append({d: i + 1 for i, d in enumerate(hits)})
+        judged_of.append(set(judged))
+    res = searcher.batch_explain(texts, qids, listed)
+    records, missing = [], 0
+    for i, qid in enumerate(qids):
+        for d, _score, rows in res[qid]:
+            if rows is None:  # the index does not hold that doc id
+                missing += 1
+                continue
+            records.append((qid, d, hits_of[i].get(d, 0), d in judged_of[i], rows))
+    print("Sparse explain: {} (query, doc) pairs, {} matched tokens, missing {}".format(
+        len(records), sum(len(r[4]) for r in records), missing))
+    if a.save_dir:
+        write_tsv(os.path.join(a.save_dir, "sparse.explain.tsv"), records)
 
 
 def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids):
@@ -505,6 +556,11 @@ def main(argv=None):
                    help="sparse search: after the search, the EXACT rank (no depth limit) of every query's --qrels docs "
                         "from one msr_rank_docs call; prints recall, MRR, MedR, MeanR and writes sparse.ranks.tsv under "
                         "--save_dir; honours --remove_query; not with --passage_reps or under a launcher")
+    s.add_argument("--explain", type=int, default=None, metavar="N",
+                   help="sparse search: after the search, WHY the first N hits of every query (1 <= N <= 64; after "
+                        "--remove_query's filter) and, with --qrels, its judged docs score what they score: per-token "
+                        "query weight x doc weight from one msr_explain_docs call; writes sparse.explain.tsv under "
+                        "--save_dir; not with --passage_reps or under a launcher")
     s.add_argument("--compat-denominator", "--compat_denominator", dest="compat_denominator", action="store_true",
                    help="multi-rank: keep the sampler's padded repeats and divide by len(shard) * world like the reference")
     s.set_defaults(fn=_cmd_search)

@@ -12,6 +12,7 @@
 
 #include "msr_kernels.hpp"
 #include "msr_rank.hpp"
+#include "msr_explain.hpp"
 
 namespace msr {
 
@@ -120,6 +121,27 @@ static int launch_rank(hipStream_t st, uint32_t tile_docs, bool count, uint32_t 
             case 8192: MSR_RANK_LAUNCH(8192, 512, 4, 8)
             case 4096: MSR_RANK_LAUNCH(4096, 256, 4, 6)
 #undef MSR_RANK_LAUNCH
+            default:
+                set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
+                return MSR_E_RANGE;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return MSR_OK;
+}
+
+// explain_tiles (msr_explain.hpp) over pairs [0, n_pairs) of a0.pairs: 1-D grid, sliced at the gather's grid limit.
+static int launch_explain(hipStream_t st, uint32_t tile_docs, uint32_t n_pairs, const ExplainArgs& a0) {
+    for (uint32_t o0 = 0; o0 < n_pairs; o0 += kRankMaxGridX) {
+        ExplainArgs a = a0;
+        a.pairs = a0.pairs + o0;
+        const dim3 grid(std::min<uint32_t>(kRankMaxGridX, n_pairs - o0));
+        switch (tile_docs) {
+            case 32768: hipLaunchKernelGGL((explain_tiles<32768>), grid, dim3(256), 0, st, a); break;
+            case 16384: hipLaunchKernelGGL((explain_tiles<16384>), grid, dim3(256), 0, st, a); break;
+            case 12288: hipLaunchKernelGGL((explain_tiles<12288>), grid, dim3(256), 0, st, a); break;
+            case 8192: hipLaunchKernelGGL((explain_tiles<8192>), grid, dim3(256), 0, st, a); break;
+            case 4096: hipLaunchKernelGGL((explain_tiles<4096>), grid, dim3(256), 0, st, a); break;
             default:
                 set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
                 return MSR_E_RANGE;
@@ -1218,6 +1240,171 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
     if (ms && (!try_hip(hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
                !try_hip(hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
         return done(MSR_E_HIP);
+    return done(MSR_OK);
+}
+
+// ------------------------------------------------------------------------------------------------ explain listed docs
+int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq,
+                     uint32_t flags, const int64_t* t_ptr, const uint32_t* t_ord, uint32_t* out_doc_w, int64_t out_cap,
+                     float ms[1]) {
+    // ---- argument checks: no device needed
+    if (!ix || !q_ptr || !t_ptr || !out_doc_w || nq < 0) {
+        set_error("msr_explain_docs: bad argument");
+        return MSR_E_INVAL;
+    }
+    if (t_ptr[0] != 0) {
+        set_error("msr_explain_docs: t_ptr must start at 0");
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i)
+        if (t_ptr[i + 1] < t_ptr[i]) {
+            set_error("msr_explain_docs: t_ptr decreases at query %d", i);
+            return MSR_E_INVAL;
+        }
+    const int64_t n_ent64 = t_ptr[nq];
+    if (n_ent64 > 0 && !t_ord) {
+        set_error("msr_explain_docs: null t_ord");
+        return MSR_E_INVAL;
+    }
+    if (q_ptr[0] < 0) {
+        set_error("msr_explain_docs: q_ptr is negative");
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i)
+        if (q_ptr[i + 1] < q_ptr[i]) {
+            set_error("msr_explain_docs: q_ptr is not monotone at query %d", i);
+            return MSR_E_INVAL;
+        }
+    if (q_ptr[nq] > 0 && (!q_term || !q_w)) {
+        set_error("msr_explain_docs: bad CSR arrays");
+        return MSR_E_INVAL;
+    }
+    const IndexHeader* h = ix->host.h;
+    if (ix->term_nshards > 0 || ix->shard_ntiles != h->n_tiles) {
+        set_error("msr_explain_docs: the weights of a doc lie in every term's segments of its tile; this handle is a %s "
+                  "shard (open the whole index with msr_index_open)", ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    uint64_t need = 0;  // u32 slots of the ragged output (saturating)
+    for (int i = 0; i < nq; ++i) {
+        const uint64_t len = (uint64_t)(q_ptr[i + 1] - q_ptr[i]), cnt = (uint64_t)(t_ptr[i + 1] - t_ptr[i]);
+        const uint64_t add = (len && cnt > (uint64_t)INT64_MAX / len) ? (uint64_t)INT64_MAX : len * cnt;
+        need = std::min<uint64_t>((uint64_t)INT64_MAX, need + add);
+    }
+    if (out_cap < 0 || (uint64_t)out_cap < need) {
+        set_error("msr_explain_docs: out_cap = %lld is below the %llu slots the listed docs own", (long long)out_cap,
+                  (unsigned long long)need);
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i)
+        if (t_ptr[i + 1] - t_ptr[i] > MSR_EXPLAIN_MAX_TARGETS) {
+            set_error("msr_explain_docs: query %d lists %lld docs (at most MSR_EXPLAIN_MAX_TARGETS = %d)", i,
+                      (long long)(t_ptr[i + 1] - t_ptr[i]), MSR_EXPLAIN_MAX_TARGETS);
+            return MSR_E_RANGE;
+        }
+    for (int64_t e = 0; e < n_ent64; ++e)
+        if ((uint64_t)t_ord[e] >= h->n_docs) {
+            set_error("msr_explain_docs: ordinal %u (entry %lld) is outside the index (%llu docs)", t_ord[e], (long long)e,
+                      (unsigned long long)h->n_docs);
+            return MSR_E_RANGE;
+        }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = 0.f;
+    if (nq == 0 || n_ent64 == 0 || need == 0) return MSR_OK;
+    if (need > 0xFFFFFFF0ull) {
+        set_error("msr_explain_docs: the listed docs own %llu output slots, more than one call serves (split the batch)",
+                  (unsigned long long)need);
+        return MSR_E_RANGE;
+    }
+    DeviceIndex* d = ix->dev;
+    // ---- the search path's normalisation, run for its refusals only (MSR_E_OVERFLOW / MSR_E_RANGE, term ids checked):
+    // the kernel below reads none of the batch's arrays
+    msr_batch* b = nullptr;
+    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
+    if (rc != MSR_OK) return rc;
+    // ---- the tables the kernel reads (msr_explain_plan.hpp: plain host code). A repeated target of a query is listed
+    // once; its row is copied below, after the download
+    const uint32_t tile = h->tile_docs;
+    ExplainPlan pl;
+    explain_plan(ix->host, q_ptr, q_term, q_w, nq, flags, t_ptr, t_ord, pl);
+    const std::vector<uint32_t>&qr = pl.q_range, &ents = pl.ents, &pairs = pl.pairs, &x_off = pl.x_off;
+    const std::vector<ExplainPlan::Item>& its = pl.items;
+    const uint32_t n_pairs = (uint32_t)(pairs.size() / 4);
+    // one upload block: pairs (uint4) | items (uint2) | entry ranges (uint2) | entries (uint2)
+    auto al = [](size_t n) { return (n + 63) / 64 * 64; };
+    const size_t o_pairs = 0, o_items = o_pairs + al(pairs.size()), o_qr = o_items + al(its.size() * 2),
+                 o_ents = o_qr + al(qr.size()), in_words = o_ents + al(ents.size());
+    std::vector<uint32_t> blk(std::max<size_t>(in_words, 1), 0u);
+    if (!pairs.empty()) memcpy(blk.data() + o_pairs, pairs.data(), pairs.size() * 4);
+    for (size_t i = 0; i < its.size(); ++i) {
+        blk[o_items + 2 * i] = its[i].row;
+        blk[o_items + 2 * i + 1] = its[i].local;
+    }
+    memcpy(blk.data() + o_qr, qr.data(), qr.size() * 4);
+    if (!ents.empty()) memcpy(blk.data() + o_ents, ents.data(), ents.size() * 4);
+    const size_t in_bytes = blk.size() * 4, out_bytes = (size_t)need * 4;
+    uint32_t* d_in = (uint32_t*)d->pool.alloc(in_bytes);
+    uint32_t* d_out = (uint32_t*)d->pool.alloc(out_bytes);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto done = [&](int r) {
+        if (r != MSR_OK) (void)hipStreamSynchronize(d->stream);  // nothing in flight may still use the scratch
+        d->pool.release(d_in, in_bytes);
+        d->pool.release(d_out, out_bytes);
+        for (hipEvent_t e : ev) {
+            if (!e) continue;
+            if (d->spare_events.size() < 64)
+                d->spare_events.push_back(e);
+            else
+                (void)hipEventDestroy(e);
+        }
+        batch_free(b);
+        return r;
+    };
+    if (!d_in || !d_out) {
+        set_error("msr_explain_docs: device allocation failed (%zu bytes of doc weights)", out_bytes);
+        return done(MSR_E_NOMEM);
+    }
+    auto try_hip = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return true;
+        set_error("msr_explain_docs: %s failed: %s", what, hipGetErrorString(e));
+        return false;
+    };
+    if (!try_hip(hipMemcpy(d_in, blk.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return done(MSR_E_HIP);
+    for (int i = 0; ms && i < 2; ++i) {
+        if (!d->spare_events.empty()) {
+            ev[i] = d->spare_events.back();
+            d->spare_events.pop_back();
+        } else if (!try_hip(hipEventCreate(&ev[i]), "hipEventCreate")) {
+            return done(MSR_E_HIP);
+        }
+    }
+    ExplainArgs xa;
+    xa.seg_ptr = d->d_seg_ptr;
+    xa.postings = d->d_postings;
+    xa.dense = d->d_dense;
+    xa.n_pairs = d->n_pairs;
+    xa.n_terms = d->seg_terms;
+    xa.vec_base = d->vec_base;
+    xa.pairs = reinterpret_cast<const uint4*>(d_in + o_pairs);
+    xa.items = reinterpret_cast<const uint2*>(d_in + o_items);
+    xa.q_range = reinterpret_cast<const uint2*>(d_in + o_qr);
+    xa.ents = reinterpret_cast<const uint2*>(d_in + o_ents);
+    xa.out = d_out;
+    if (ms && !try_hip(hipEventRecord(ev[0], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    if (!try_hip(hipMemsetAsync(d_out, 0, out_bytes, d->stream), "hipMemsetAsync")) return done(MSR_E_HIP);
+    rc = launch_explain(d->stream, tile, n_pairs, xa);
+    if (rc != MSR_OK) return done(rc);
+    if (ms && !try_hip(hipEventRecord(ev[1], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    if (!try_hip(hipStreamSynchronize(d->stream), "the explain kernel")) return done(MSR_E_HIP);
+    if (!try_hip(hipMemcpy(out_doc_w, d_out, out_bytes, hipMemcpyDeviceToHost), "download")) return done(MSR_E_HIP);
+    if (ms && !try_hip(hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime")) return done(MSR_E_HIP);
+    for (const auto& dp : pl.dups) {  // a repeated target: the row of the entry it repeats
+        const uint32_t q = (uint32_t)(std::upper_bound(t_ptr, t_ptr + nq + 1, (int64_t)dp.first) - t_ptr - 1);
+        memcpy(out_doc_w + x_off[dp.first], out_doc_w + x_off[dp.second], (size_t)(q_ptr[q + 1] - q_ptr[q]) * 4);
+    }
     return done(MSR_OK);
 }
 

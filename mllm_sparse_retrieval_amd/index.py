@@ -225,6 +225,31 @@ class SparseIndex:
                                   C.cast(ms, C.c_void_p) if with_ms else None))
         return (ranks, scores, (float(ms[0]), float(ms[1]))) if with_ms else (ranks, scores)
 
+    def explain_docs(self, q_ptr, q_term, q_w, t_ptr, t_ord, drop_df_eq_n=True, with_ms=False):
+        """Per-term doc weights of listed docs (msr_explain_docs): query i lists the ordinals t_ord[t_ptr[i]:t_ptr[i + 1]]
+        (at most MSR_EXPLAIN_MAX_TARGETS). Returns (x_ptr int64 [n_entries + 1], doc_w uint32): target entry e owns
+        doc_w[x_ptr[e]:x_ptr[e + 1]], one slot per INPUT entry of its query (slot j = entry q_ptr[i] + j), holding the
+        stored weight of that entry's term in the listed doc, or 0 when the doc lacks the term or the entry does not
+        count (term < 0, weight <= 0, dropped as df == N). sum(max(q_w, 0) * doc_w) over a row is the doc's exact score
+        (rank_docs). with_ms=True appends the HIP-event time of the explain work."""
+        q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
+        nq = len(q_ptr) - 1
+        t_ptr = np.ascontiguousarray(t_ptr, dtype=np.int64)
+        t_ord = np.ascontiguousarray(t_ord, dtype=np.uint32)
+        if t_ptr.ndim != 1 or len(t_ptr) != nq + 1 or t_ord.ndim != 1 or int(t_ptr[-1]) != len(t_ord):
+            raise ValueError("malformed CSR target arrays")
+        if t_ptr[0] != 0 or (np.diff(t_ptr) < 0).any() or (np.diff(q_ptr) < 0).any():
+            raise ValueError("malformed CSR target arrays")
+        x_ptr = np.zeros(len(t_ord) + 1, dtype=np.int64)
+        np.cumsum(np.repeat(np.diff(q_ptr), np.diff(t_ptr)), out=x_ptr[1:])
+        buf = np.zeros(max(int(x_ptr[-1]), 1), dtype=np.uint32)  # (never a null output pointer)
+        doc_w = buf[:int(x_ptr[-1])]
+        ms = (C.c_float * 1)()
+        check(lib().msr_explain_docs(self._h, ptr(q_ptr), ptr(q_term), ptr(q_w), nq, MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0,
+                                     ptr(t_ptr), ptr(t_ord), ptr(doc_w), len(doc_w),
+                                     C.cast(ms, C.c_void_p) if with_ms else None))
+        return (x_ptr, doc_w, float(ms[0])) if with_ms else (x_ptr, doc_w)
+
     def search_text(self, queries, k, drop_df_eq_n=True):
         """Query strings (tokens repeated `weight` times, src/search.py:419-422) -> the same outputs as search_csr;
         tokenisation, counting and dictionary lookup run in C inside the call."""

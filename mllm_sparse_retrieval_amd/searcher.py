@@ -148,3 +148,48 @@ class LuceneImpactSearcher:
                     row.append((d, None, None))
             out[qid] = row
         return out
+
+    def batch_explain(self, queries, qids, targets):
+        """Why named docs score what they score: targets[i] lists external doc ids for queries[i] (at most
+        MSR_EXPLAIN_MAX_TARGETS known ids each). Returns {qid: [(docid, score, rows), ...]} in the given order, rows =
+        [(token, q_w, d_w, q_w * d_w), ...] for the query tokens the doc holds (contribution descending, then token
+        bytewise; explain.rows_of) and score = their sum, the exact score batch_rank reports; an id the index does not
+        hold comes back as (docid, None, None). Counterpart: Lucene's explain(), which the reference never calls
+        (SparseIndex.explain_docs)."""
+        from .explain import build_rows, score_of
+
+        if not (len(queries) == len(qids) == len(targets)):
+            raise ValueError("queries, qids and targets differ in length")
+        table = self.index.docid_table()
+        if getattr(self, "_ord_of", None) is None:
+            self._ord_of = {d: o for o, d in enumerate(table.tolist())}
+        ord_of = self._ord_of
+        q_ptr, toks, ws = tokenize_queries(queries)  # (the tokens name the rows, so they are kept on this side)
+        term_ids = self.index.lookup(toks)
+        if self.min_idf > 0:  # as in batch_rank: the idf filter on the host
+            df = self.index.df(term_ids).astype(np.float64)
+            with np.errstate(divide="ignore"):
+                idf = np.log(self.index.n_docs / np.maximum(df, 1e-300))
+            ws = np.where((df > 0) & (idf > self.min_idf), ws, 0).astype(np.int32)
+            drop = True if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        else:
+            drop = self.min_idf >= 0 if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        t_ptr, t_ord = [0], []
+        for tg in targets:
+            t_ord.extend(ord_of[str(d)] for d in tg if str(d) in ord_of)
+            t_ptr.append(len(t_ord))
+        x_ptr, doc_w = self.index.explain_docs(q_ptr, term_ids, ws, np.asarray(t_ptr, np.int64),
+                                               np.asarray(t_ord, np.uint32), drop_df_eq_n=drop)
+        rows = build_rows(q_ptr, toks, ws.tolist(), t_ptr, x_ptr, doc_w.tolist())
+        out = {}
+        for i, qid in enumerate(qids):
+            e = t_ptr[i]
+            row = []
+            for d in targets[i]:
+                if str(d) in ord_of:
+                    row.append((d, score_of(rows[e]), rows[e]))
+                    e += 1
+                else:
+                    row.append((d, None, None))
+            out[qid] = row
+        return out

@@ -327,7 +327,18 @@ int msr_f32_to_f16(const float* src, uint16_t* dst, uint64_t n, int threads);
  *     k = depth, select_tiles over the score matrix, fuse_tiles, merges); ms = {sparse, dense GEMM, dense select, fusion}.
  * Tie rule of the DENSE depth list (two passages with bit-equal scores at the depth boundary — duplicated captions do
  * that): the first two paths keep the lower doc ORDINAL, the list-based path and msr_dense_search the lower ROW, as a
- * flat index does. Everything else (sparse ties, fused-score ties: lower ordinal) is the same on every path. */
+ * flat index does. Everything else (sparse ties, fused-score ties: lower ordinal) is the same on every path.
+ * FUSION CONTRACT. Every path computes the fused score by this f32 operation sequence, bit for bit:
+ *     w_d = (float)alpha, w_s = 1.0f - w_d;
+ *     per side: max / min = the best and the last score of the UNFILTERED depth list (self_ord still in it) — sparse:
+ *         (float)u32, dense: -0 canonicalised to +0, an empty list: 0, 0 — and inv = 1.0f / fmaxf(max - min, 1e-9f);
+ *     t(x) = 1.0f when x is the list's maximum and max > min (the sparse comparison is on the exact u32 score, not on
+ *         its f32 image), else t(x) = (x - min) * inv: one rounded subtraction, one rounded multiplication;
+ *     f = +0.0f;  f = fmaf(w_d, t_d, f) if the dense list holds the doc;  f = fmaf(w_s, t_s, f) if the sparse list does.
+ * Members are the union of the two lists minus self_ord, ordered by the fused key descending, lower ordinal first; the
+ * first k are returned, out_n = min(k, members), padding 0xFFFFFFFF / 0.f. So the same depth lists give the same
+ * ordinals and score bits on every path; only the dense tie rule above can make the lists differ. alpha outside [0, 1]
+ * is not refused (one weight is negative, fused scores may be). tests/fusion_ref.py restates the sequence in numpy. */
 int msr_hybrid_search(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
                       const uint16_t* q_fp16, int nq, int depth, int k, float alpha, uint32_t flags,
                       const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score, int32_t* out_n,
@@ -352,8 +363,8 @@ int msr_hybrid_search_f32(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, co
  * members = the union of query i's two depth lists minus self_ord[i], by fused score descending (ties: lower ordinal);
  * a member whose fused score is 0 (the depth-th doc of one list that is not in the other) IS a member. Padding:
  * 0xFFFFFFFF / 0.f as msr_hybrid_search pads, 0 in the optional arrays.
- *   out_score       the f32 fused score of msr_hybrid_search[_f32]: the first min(k, out_n[i]) entries of a row have the
- *                   ordinals and the score bits those calls return for that k on their candidate path;
+ *   out_score       the f32 fused score of msr_hybrid_search[_f32] (the FUSION CONTRACT above): the first
+ *                   min(k, out_n[i]) entries of a row have the ordinals and the score bits those calls return for that k;
  *   out_src         bit 0: in the dense depth list, bit 1: in the sparse depth list (1 / 2 / 3 = fuse_statistic's
  *                   'dense' / 'sparse' / 'fuse' with runs ordered [dense, sparse], src/search.py:459);
  *   out_sparse_u32  the exact sparse score where bit 1 is set, else 0;

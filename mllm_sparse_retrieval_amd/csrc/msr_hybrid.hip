@@ -460,7 +460,9 @@ int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t*
 // with min/max over each UNFILTERED list (get_run_dict, src/search.py:76-81) and the query's own doc skipped when
 // remove_query is set (src/search.py:72-74). Fused scores are built in an LDS accumulator tile over doc ordinals and
 // the best k are selected by the same tile_select as everywhere else. f32 arithmetic (the reference mixes f32 and
-// f64 depending on the numpy version): scores agree within the north star's 1e-5.
+// f64 depending on the numpy version): scores agree within the north star's 1e-5. The f32 operation sequence is the
+// one of the contract in include/msr.h (msr_hybrid_search) — the quotient as a multiplication by the reciprocal, exactly
+// 1 at the maximum, two fused adds — so this path returns the score bits of hybrid_tiles and hybrid_fuse_query.
 namespace msr {
 
 struct FuseArgs {
@@ -482,7 +484,6 @@ __global__ __launch_bounds__(NT) void fuse_tiles(const FuseArgs a) {
     using L = TileLds<TILE_DOCS, NT, CAND>;
     __shared__ __attribute__((aligned(16))) uint8_t lds[L::kTotal];
     __shared__ uint8_t member[TILE_DOCS];
-    __shared__ float mm[4];  // min_s, den_s, min_d, den_d
     uint32_t* const acc = reinterpret_cast<uint32_t*>(lds);
     float* const facc = reinterpret_cast<float*>(lds);
     uint8_t* const un = lds + L::kAcc;
@@ -548,21 +549,21 @@ __global__ __launch_bounds__(NT) void fuse_tiles(const FuseArgs a) {
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        const bool has_s = mmu[1] != 0, has_d = mmu[3] != 0;  // (sparse scores and dense keys of hits are non-zero)
-        const float smax = has_s ? (float)mmu[1] : 0.f, smin = has_s ? (float)mmu[0] : 0.f;
-        const float dmax = has_d ? key_to_f32(mmu[3]) : 0.f, dmin = has_d ? key_to_f32(mmu[2]) : 0.f;
-        mm[0] = smin;
-        mm[1] = fmaxf(smax - smin, 1e-9f);
-        mm[2] = dmin;
-        mm[3] = fmaxf(dmax - dmin, 1e-9f);
-    }
-    __syncthreads();
+    // The fusion arithmetic of the contract (include/msr.h, msr_hybrid_search), the one hybrid_tiles and
+    // hybrid_fuse_query compute: reciprocal of the spread, EXACTLY 1 at the list's maximum (the sparse comparison on the
+    // u32 score), two fused adds from +0. Every thread derives the per-side constants for itself.
+    const uint32_t smax_u = mmu[1];
+    const bool has_s = smax_u != 0, has_d = mmu[3] != 0;  // (sparse scores and dense keys of hits are non-zero)
+    const float smax = has_s ? (float)smax_u : 0.f, smin = has_s ? (float)mmu[0] : 0.f;
+    const float dmax = has_d ? key_to_f32(mmu[3]) + 0.0f : 0.f, dmin = has_d ? key_to_f32(mmu[2]) + 0.0f : 0.f;
+    const float inv_sden = 1.0f / fmaxf(smax - smin, 1e-9f), inv_dden = 1.0f / fmaxf(dmax - dmin, 1e-9f);
+    const bool spread_s = smax > smin, spread_d = dmax > dmin;
     // dense pass first (the reference adds the dense term first), then the sparse pass; docs are unique per list
     for (int j = tid; j < dn; j += NT) {
         const uint32_t ord = a.row2ord[di[j]];
         if (ord != self && ord >= doc0 && ord < doc0 + ndocs_tile) {
-            facc[ord - doc0] = a.w_dense * ((key_to_f32(dk[j]) - mm[2]) / mm[3]);
+            const float d = key_to_f32(dk[j]) + 0.0f;
+            facc[ord - doc0] = __builtin_fmaf(a.w_dense, (d == dmax && spread_d) ? 1.0f : (d - dmin) * inv_dden, 0.f);
             member[ord - doc0] = 1;
         }
     }
@@ -572,7 +573,9 @@ __global__ __launch_bounds__(NT) void fuse_tiles(const FuseArgs a) {
         if (!key) continue;
         const uint32_t ord = 0xFFFFFFFFu - (uint32_t)key;
         if (ord != self && ord >= doc0 && ord < doc0 + ndocs_tile) {
-            facc[ord - doc0] += a.w_sparse * (((float)(uint32_t)(key >> 32) - mm[0]) / mm[1]);
+            const uint32_t sv = (uint32_t)(key >> 32);
+            facc[ord - doc0] = __builtin_fmaf(a.w_sparse, (sv == smax_u && spread_s) ? 1.0f : ((float)sv - smin) * inv_sden,
+                                              facc[ord - doc0]);
             member[ord - doc0] = 1;
         }
     }
@@ -1002,8 +1005,10 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void hybrid_tiles(const ScoreArgs a,
                 const bool in_d = d > td_f || (d == td_f && inv >= td_inv);
                 const bool in_s = s4[e] != 0 && (s4[e] > ts_key || (s4[e] == ts_key && inv >= ts_inv));
                 float f = 0.f;  // the reference adds the dense term first (runs = [dense, sparse], src/search.py:459)
-                if (in_d) f += h.w_dense * ((d == dmax && spread_d) ? 1.0f : (d - dmin) * inv_dden);
-                if (in_s) f += h.w_sparse * ((s4[e] == smax_u && spread_s) ? 1.0f : ((float)s4[e] - smin) * inv_sden);
+                // (the two adds are FUSED by contract, include/msr.h: spelled out, not left to -ffp-contract)
+                if (in_d) f = __builtin_fmaf(h.w_dense, (d == dmax && spread_d) ? 1.0f : (d - dmin) * inv_dden, f);
+                if (in_s)
+                    f = __builtin_fmaf(h.w_sparse, (s4[e] == smax_u && spread_s) ? 1.0f : ((float)s4[e] - smin) * inv_sden, f);
                 const bool member = (in_d || in_s) && local != self;
                 fk[e] = member ? f32_to_key(f) : 0u;
                 if (member) {
@@ -1354,9 +1359,10 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
         float f = 0.f;
         if (in_d) {  // (EXACTLY 1 at the maximum, as the reference's quotient is: see hybrid_tiles)
             const float d = key_to_f32(dv) + 0.0f;
-            f += h.w_dense * ((d == dmax && spread_d) ? 1.0f : (d - dmin) * inv_dden);
+            f = __builtin_fmaf(h.w_dense, (d == dmax && spread_d) ? 1.0f : (d - dmin) * inv_dden, f);
         }
-        if (in_s) f += h.w_sparse * ((sv == smax_u && spread_s) ? 1.0f : ((float)sv - smin) * inv_sden);
+        // (the two adds are FUSED by contract, include/msr.h: spelled out, not left to -ffp-contract)
+        if (in_s) f = __builtin_fmaf(h.w_sparse, (sv == smax_u && spread_s) ? 1.0f : ((float)sv - smin) * inv_sden, f);
         return ((uint64_t)f32_to_key(f) << 32) | (uint64_t)(0xFFFFFFFFu - o);
     };
     // the fused keys replace the records in the registers (16 x u64 for 48 x u32; UNION keeps both)

@@ -189,14 +189,30 @@ def union_oracle_runs(docs, n_terms, ids, qp, qt, qw, sample, depth, remove, qid
     return o_sparse, o_dense, exact, sq
 
 
+def assert_union_arithmetic(res, alpha, smax_u=None):
+    """One msr_hybrid_search_union result against tests/fusion_ref.refuse_union: every member's fused score, bit for bit,
+    and the whole order (fused key descending, lower ordinal first) follow from out_src, out_sparse_u32, out_dense and
+    out_range by the contract of include/msr.h. Exact equality, padding included."""
+    from tests import fusion_ref
+
+    ords, fs, cnt, src, su, de, rng = res[:7]
+    want_ords, want_bits = fusion_ref.refuse_union(ords, cnt, src, su, de, rng, alpha, smax_u=smax_u)
+    got_bits = np.ascontiguousarray(fs, dtype=np.float32).view(np.uint32)
+    bad = np.flatnonzero((want_bits != got_bits).any(axis=1) | (want_ords != ords).any(axis=1))
+    assert len(bad) == 0, ("fused bits or order differ from the contract in queries", bad[:10].tolist())
+
+
 def check_union(res, sample, sq, o_sparse, o_dense, exact, alpha, depth, ix, dense_of):
     """Everything tests 1-3 of the union ask of one result: exact membership and fused order (assert_hybrid_matches at
-    k = 2 x depth plus set equality), the side arrays, the padding, and union_to_runs against the oracle's run dicts.
+    k = 2 x depth plus set equality), the side arrays, the padding, and union_to_runs against the oracle's run dicts —
+    and, on EVERY query of the call, the fused score bits and the order recomputed from the call's own outputs by the
+    contract's f32 operation sequence (assert_union_arithmetic).
     dense_of(j, doc) -> the f32 dense score the call must report for sample query j and that doc."""
     from mllm_sparse_retrieval_amd import fusion
     from oracle import oracle
 
     ords, fs, cnt, src, su, de, rng, _ = res
+    assert_union_arithmetic(res, alpha)
     w = 2 * depth
     assert ords.shape == fs.shape == src.shape == su.shape == de.shape == (len(cnt), w) and rng.shape == (len(cnt), 4)
     want = oracle.fuse([o_dense, o_sparse], [alpha, 1 - alpha])

@@ -1293,8 +1293,10 @@ def test_multitile_hybrid_randomised(m, tmp_path, monkeypatch):
     4096 or 8192 docs incl. a last tile of one doc, depths 1-1024, k 1-1024, alpha incl. 0 and 1, remove_query, empty and
     short queries, small vocabularies (mass ties on the sparse side), duplicated passage rows (exact dense ties), and — every
     third case — a forced quota of 1-40 candidates per tile, so that hybrid_fuse_query's verification has to send queries
-    to the second round. (MSR_FUZZ_SEED / MSR_FUZZ_CASES as in the other fuzz tests.)"""
-    from mllm_sparse_retrieval_amd.dense import DenseIndex, hybrid_search, row_to_ordinal
+    to the second round. (MSR_FUZZ_SEED / MSR_FUZZ_CASES as in the other fuzz tests.) One msr_hybrid_search_union call per
+    case pins what the tolerances above leave open: its fused bits and its order follow exactly from its own side arrays
+    (helpers.assert_union_arithmetic), and the top-k call returns its first k ordinals and score bits."""
+    from mllm_sparse_retrieval_amd.dense import DenseIndex, hybrid_search, hybrid_search_union, row_to_ordinal
 
     rng = np.random.default_rng(int(os.environ.get("MSR_FUZZ_SEED", "20261005")))
     for case in range(int(os.environ.get("MSR_FUZZ_CASES", "12"))):
@@ -1352,6 +1354,13 @@ def test_multitile_hybrid_randomised(m, tmp_path, monkeypatch):
                     assert abs(float(fs[i, r]) - float(score)) <= tol, (case, i, r, float(fs[i, r]), float(score), tol)
                 if remove:
                     assert qids[i] not in got
+            un = hybrid_search_union(ix, dix, qp, qt, qw, q, depth, alpha, r2o, self_ord)
+            helpers.assert_union_arithmetic(un, alpha)
+            kk = min(k, 2 * depth)
+            assert (cnt == np.minimum(un[2], k)).all(), case
+            assert (ords[:, :kk] == un[0][:, :kk]).all() and (ords[:, kk:] == 0xFFFFFFFF).all(), case
+            assert (fs.view(np.uint32)[:, :kk] == un[1].view(np.uint32)[:, :kk]).all(), case
+            assert (fs.view(np.uint32)[:, kk:] == 0).all(), case
             dix.close()
         os.remove(path)
     monkeypatch.delenv("MSR_HYBRID_QUOTA", raising=False)

@@ -26,29 +26,20 @@ static int launch_score(hipStream_t st, uint32_t tile_docs, uint32_t t_begin, ui
         ScoreArgs a = a0;
         a.tl0 = tl0;
         const dim3 grid(a.qn, std::min<uint32_t>(kMaxGridY, t_end - tl0));
-        switch (tile_docs) {
-#define MSR_LAUNCH(T, N, UU, W, WR)                                                                \
-    if (dump)                                                                                      \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 512, 1>), grid, dim3(N), 0, st, a);          \
-    else if (a.k <= 512 && a.light && (T == 8192 || T == 4096))                                    \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512, 0, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a); \
-    else if (a.k <= 512)                                                                           \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512>), grid, dim3(N), 0, st, a);              \
-    else                                                                                           \
-        hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 1024>), grid, dim3(N), 0, st, a);            \
-    break;
-            // <tile, threads, chunk loads per bank, min waves/SIMD of the k <= 512 instance, of the other instances>
-            // LDS per workgroup = 4 B x tile + 4-8 KiB candidates + maxima -> workgroups (waves) per CU:
-            case 32768: MSR_LAUNCH(32768, 1024, 8, 4, 4)  // 1 (16)
-            case 16384: MSR_LAUNCH(16384, 512, 8, 4, 4)   // 2 (16)
-            case 12288: MSR_LAUNCH(12288, 512, 4, 4, 4)   // 2 (16)
-            case 8192: MSR_LAUNCH(8192, 512, 4, 8, 6)     // 4 (32) with k <= 512, 3 (24) above
-            case 4096: MSR_LAUNCH(4096, 256, 4, 6, 5)     // 7 (28)
-#undef MSR_LAUNCH
-            default:
-                set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
-                return MSR_E_RANGE;
-        }
+        // the instance: dump / light with the 512-key buffer / k <= 512 / the 1024-key buffer, in this order
+        const bool known = with_tile_shape(tile_docs, [&](auto s) {
+            using S = decltype(s);
+            constexpr uint32_t T = S::docs, N = S::threads, UU = S::loads, W = S::waves, WR = S::waves_rest;
+            if (dump)
+                hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 512, 1>), grid, dim3(N), 0, st, a);
+            else if (a.k <= 512 && a.light && S::light)
+                hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512, 0, S::light>), grid, dim3(N), 0, st, a);
+            else if (a.k <= 512)
+                hipLaunchKernelGGL((score_tiles<T, N, UU, W, 512>), grid, dim3(N), 0, st, a);
+            else
+                hipLaunchKernelGGL((score_tiles<T, N, UU, WR, 1024>), grid, dim3(N), 0, st, a);
+        });
+        if (!known) return no_tile_shape(tile_docs);
         HIP_TRY(hipGetLastError());
     }
     return MSR_OK;
@@ -61,16 +52,11 @@ int launch_select(hipStream_t st, uint32_t tile_docs, const SelectArgs& a) {
         return MSR_E_RANGE;
     }
     const dim3 grid(a.qn, a.tpr);  // x = query, y = tile of the rank's range
-    switch (tile_docs) {
-        case 32768: hipLaunchKernelGGL((select_tiles<32768, 1024, 1024>), grid, dim3(1024), 0, st, a); break;
-        case 16384: hipLaunchKernelGGL((select_tiles<16384, 512, 1024>), grid, dim3(512), 0, st, a); break;
-        case 12288: hipLaunchKernelGGL((select_tiles<12288, 512, 1024>), grid, dim3(512), 0, st, a); break;
-        case 8192: hipLaunchKernelGGL((select_tiles<8192, 512, 1024>), grid, dim3(512), 0, st, a); break;
-        case 4096: hipLaunchKernelGGL((select_tiles<4096, 256, 1024>), grid, dim3(256), 0, st, a); break;
-        default:
-            set_error("no kernel instance for tile_docs=%u", tile_docs);
-            return MSR_E_RANGE;
-    }
+    const bool known = with_tile_shape(tile_docs, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((select_tiles<S::docs, S::threads, 1024>), grid, dim3(S::threads), 0, st, a);
+    });
+    if (!known) return no_tile_shape(tile_docs);
     HIP_TRY(hipGetLastError());
     return MSR_OK;
 }
@@ -85,8 +71,8 @@ int launch_merge(hipStream_t st, const MergeArgs& a) {
     return MSR_OK;
 }
 
-// The rank kernels (msr_rank.hpp) at the accumulation's launch shapes: the <tile, threads, chunk loads per bank, min
-// waves/SIMD of the k <= 512 instance> columns of launch_score's table, the light instance chosen by the same rule.
+// The rank kernels (msr_rank.hpp) at the accumulation's launch shapes (the k <= 512 instance's waves), the light instance
+// chosen by launch_score's rule.
 // count = false: rank_gather_tiles over pairs [0, n_pairs) of a.pairs (1-D grid);
 // count = true:  rank_count_tiles over queries [a0.s.q0, a0.s.q0 + a0.s.qn) x shard-local tiles [0, t_end).
 constexpr uint32_t kRankMaxGridX = 1u << 30;  // pairs per gather launch (HIP grid limit in x: 2^31 - 1)
@@ -104,27 +90,19 @@ static int launch_rank(hipStream_t st, uint32_t tile_docs, bool count, uint32_t 
             a.pairs = a0.pairs + o0;
         }
         const bool light = a.s.light != 0;
-        switch (tile_docs) {
-#define MSR_RANK_LAUNCH(T, N, UU, W)                                                                               \
-    if (count && light)                                                                                            \
-        hipLaunchKernelGGL((rank_count_tiles<T, N, UU, W, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a);    \
-    else if (count)                                                                                                \
-        hipLaunchKernelGGL((rank_count_tiles<T, N, UU, W, false>), grid, dim3(N), 0, st, a);                       \
-    else if (light)                                                                                                \
-        hipLaunchKernelGGL((rank_gather_tiles<T, N, UU, W, (T == 8192 || T == 4096)>), grid, dim3(N), 0, st, a);   \
-    else                                                                                                           \
-        hipLaunchKernelGGL((rank_gather_tiles<T, N, UU, W, false>), grid, dim3(N), 0, st, a);                      \
-    break;
-            case 32768: MSR_RANK_LAUNCH(32768, 1024, 8, 4)
-            case 16384: MSR_RANK_LAUNCH(16384, 512, 8, 4)
-            case 12288: MSR_RANK_LAUNCH(12288, 512, 4, 4)
-            case 8192: MSR_RANK_LAUNCH(8192, 512, 4, 8)
-            case 4096: MSR_RANK_LAUNCH(4096, 256, 4, 6)
-#undef MSR_RANK_LAUNCH
-            default:
-                set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
-                return MSR_E_RANGE;
-        }
+        const bool known = with_tile_shape(tile_docs, [&](auto s) {
+            using S = decltype(s);
+            constexpr uint32_t T = S::docs, N = S::threads, UU = S::loads, W = S::waves;
+            if (count && light)
+                hipLaunchKernelGGL((rank_count_tiles<T, N, UU, W, S::light>), grid, dim3(N), 0, st, a);
+            else if (count)
+                hipLaunchKernelGGL((rank_count_tiles<T, N, UU, W, false>), grid, dim3(N), 0, st, a);
+            else if (light)
+                hipLaunchKernelGGL((rank_gather_tiles<T, N, UU, W, S::light>), grid, dim3(N), 0, st, a);
+            else
+                hipLaunchKernelGGL((rank_gather_tiles<T, N, UU, W, false>), grid, dim3(N), 0, st, a);
+        });
+        if (!known) return no_tile_shape(tile_docs);
         HIP_TRY(hipGetLastError());
     }
     return MSR_OK;
@@ -136,16 +114,9 @@ static int launch_explain(hipStream_t st, uint32_t tile_docs, uint32_t n_pairs, 
         ExplainArgs a = a0;
         a.pairs = a0.pairs + o0;
         const dim3 grid(std::min<uint32_t>(kRankMaxGridX, n_pairs - o0));
-        switch (tile_docs) {
-            case 32768: hipLaunchKernelGGL((explain_tiles<32768>), grid, dim3(256), 0, st, a); break;
-            case 16384: hipLaunchKernelGGL((explain_tiles<16384>), grid, dim3(256), 0, st, a); break;
-            case 12288: hipLaunchKernelGGL((explain_tiles<12288>), grid, dim3(256), 0, st, a); break;
-            case 8192: hipLaunchKernelGGL((explain_tiles<8192>), grid, dim3(256), 0, st, a); break;
-            case 4096: hipLaunchKernelGGL((explain_tiles<4096>), grid, dim3(256), 0, st, a); break;
-            default:
-                set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
-                return MSR_E_RANGE;
-        }
+        const bool known = with_tile_shape(
+            tile_docs, [&](auto s) { hipLaunchKernelGGL((explain_tiles<decltype(s)::docs>), grid, dim3(256), 0, st, a); });
+        if (!known) return no_tile_shape(tile_docs);
         HIP_TRY(hipGetLastError());
     }
     return MSR_OK;
@@ -165,12 +136,7 @@ int device_attach(msr_index* ix, int device) {
         return MSR_E_NODEVICE;
     }
     const IndexHeader* h = ix->host.h;
-    switch (h->tile_docs) {
-        case 4096: case 8192: case 12288: case 16384: case 32768: break;
-        default:
-            set_error("index tile_docs=%u has no kernel instance (supported: 4096, 8192, 12288, 16384, 32768)", h->tile_docs);
-            return MSR_E_RANGE;
-    }
+    if (!tile_threads(h->tile_docs)) return no_tile_shape(h->tile_docs);
     DeviceIndex* d = new (std::nothrow) DeviceIndex;
     if (!d) {
         set_error("out of host memory");
@@ -394,8 +360,6 @@ static void compute_df_shard(msr_index* ix) {
 // ================================================================================================ batches
 using namespace msr;
 
-
-
 // Device buffers and events of a batch go back to the handle (pool, spare events). Needs the index alive: once the
 // index is closed the batch is detached (b->ix == nullptr) and holds nothing on the device any more.
 void batch_release_device(msr_batch* b) {
@@ -415,13 +379,7 @@ void batch_release_device(msr_batch* b) {
     b->d_sf32 = nullptr;
     b->d_n = nullptr;
     b->d_part = b->d_keys = nullptr;
-    for (hipEvent_t e : b->events) {
-        if (!e) continue;
-        if (d->spare_events.size() < 64)
-            d->spare_events.push_back(e);
-        else
-            (void)hipEventDestroy(e);
-    }
+    for (hipEvent_t e : b->events) d->return_event(e);
     b->events.clear();
     b->ev0 = b->ev1 = b->ev2 = nullptr;
     b->calls = 0;
@@ -451,9 +409,26 @@ static int batch_alive(const msr_batch* b, const char* who) {
     return MSR_OK;
 }
 
-extern "C" {
-
-}  // extern "C"
+// A timed search call begins: it gets its own event triple (borrowed from the handle), so that a whole timed region
+// can be summed afterwards, and ev0 is recorded.
+static int batch_begin_timed(msr_batch* b) {
+    DeviceIndex* d = b->ix->dev;
+    if (b->calls >= 4096) b->calls = 0;  // bounded: callers that never reset keep only the recent calls
+    while (b->events.size() < (b->calls + 1) * 3) {
+        hipEvent_t e = d->borrow_event();
+        if (!e) {
+            set_error("hipEventCreate failed");
+            return MSR_E_HIP;
+        }
+        b->events.push_back(e);
+    }
+    b->ev0 = b->events[b->calls * 3 + 0];
+    b->ev1 = b->events[b->calls * 3 + 1];
+    b->ev2 = b->events[b->calls * 3 + 2];
+    b->calls++;
+    HIP_TRY(hipEventRecord(b->ev0, d->stream));
+    return MSR_OK;
+}
 
 // small = msr_search_csr's own batch: no HIP events, and — when the result block fits — results written straight to
 // mapped host memory
@@ -783,25 +758,8 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
     DeviceIndex* d = ix->dev;
     const IndexHeader* h = ix->host.h;
     HIP_TRY(hipSetDevice(d->device));
-    // every call gets its own event triple so that a whole timed region can be summed afterwards
-    if (b->calls >= 4096) b->calls = 0;  // bounded: callers that never reset keep only the recent calls
-    while (!b->untimed && b->events.size() < (b->calls + 1) * 3) {
-        hipEvent_t e = nullptr;
-        if (!d->spare_events.empty()) {
-            e = d->spare_events.back();
-            d->spare_events.pop_back();
-        } else {
-            HIP_TRY(hipEventCreate(&e));
-        }
-        b->events.push_back(e);
-    }
-    if (!b->untimed) {
-        b->ev0 = b->events[b->calls * 3 + 0];
-        b->ev1 = b->events[b->calls * 3 + 1];
-        b->ev2 = b->events[b->calls * 3 + 2];
-        b->calls++;
-        HIP_TRY(hipEventRecord(b->ev0, d->stream));
-    }
+    if (!b->untimed)
+        if (int rc0 = batch_begin_timed(b)) return rc0;
     ScoreArgs sa;
     fill_score_args(sa, b, k);
     sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;
@@ -988,7 +946,7 @@ int msr_batch_work(const msr_batch* b, uint64_t out[6]) {
     const msr_index* ix = b->ix;
     const IndexHeader* h = ix->host.h;
     // threads of the scoring instance (4 accumulators per thread and round)
-    const uint64_t nt = h->tile_docs == 4096 ? 256 : (h->tile_docs == 32768 ? 1024 : 512);
+    const uint64_t nt = tile_threads(h->tile_docs);
     uint64_t acc_words = 0;  // accumulators one query initialises (and selects over) across the shard's tiles
     for (uint32_t t = ix->shard_tile0; t < ix->shard_tile0 + ix->shard_ntiles; ++t) {
         const uint64_t docs = std::min<uint64_t>(h->tile_docs, h->n_docs - (uint64_t)t * h->tile_docs);
@@ -1046,6 +1004,65 @@ int msr_search_laps(double out_us[8]) {
     return MSR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ listed docs
+// The argument checks msr_rank_docs and msr_explain_docs share (`who` names the caller in the messages); none needs a
+// device. First the shapes (MSR_E_INVAL): null arguments, the CSR rows of the listed docs, a shard handle ...
+static int listed_check_shapes(const char* who, const msr_index* ix, bool args_ok, int nq, const int64_t* t_ptr,
+                               const uint32_t* t_ord) {
+    if (!args_ok) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if (t_ptr[0] != 0) {
+        set_error("%s: t_ptr must start at 0", who);
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i)
+        if (t_ptr[i + 1] < t_ptr[i]) {
+            set_error("%s: t_ptr decreases at query %d", who, i);
+            return MSR_E_INVAL;
+        }
+    if (t_ptr[nq] > 0 && !t_ord) {
+        set_error("%s: null t_ord", who);
+        return MSR_E_INVAL;
+    }
+    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
+        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
+                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    return MSR_OK;
+}
+
+// ... then the ranges (MSR_E_RANGE): listed docs per query, ordinals (self_ord: msr_rank_docs only, may be null), and
+// last the device (MSR_E_NODEVICE).
+static int listed_check_ranges(const char* who, const msr_index* ix, int nq, const int64_t* t_ptr, const uint32_t* t_ord,
+                               const int32_t* self_ord, int max_targets, const char* max_name) {
+    const uint64_t n_docs = ix->host.h->n_docs;
+    for (int i = 0; i < nq; ++i) {
+        if (t_ptr[i + 1] - t_ptr[i] > max_targets) {
+            set_error("%s: query %d lists %lld docs (at most %s = %d)", who, i, (long long)(t_ptr[i + 1] - t_ptr[i]), max_name,
+                      max_targets);
+            return MSR_E_RANGE;
+        }
+        if (self_ord && self_ord[i] >= 0 && (uint64_t)self_ord[i] >= n_docs) {
+            set_error("%s: self_ord[%d] = %d is outside the index (%llu docs)", who, i, self_ord[i], (unsigned long long)n_docs);
+            return MSR_E_RANGE;
+        }
+    }
+    for (int64_t e = 0; e < t_ptr[nq]; ++e)
+        if ((uint64_t)t_ord[e] >= n_docs) {
+            set_error("%s: ordinal %u (entry %lld) is outside the index (%llu docs)", who, t_ord[e], (long long)e,
+                      (unsigned long long)n_docs);
+            return MSR_E_RANGE;
+        }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    return MSR_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ exact ranks
 // Queries of one count pass: the [tile][entry] partial counts of a pass are device scratch (tiles x entries of the pass
 // x 4 bytes, at most MSR_RANK_MAX_TARGETS entries per query), so a big batch is ranked kRankPassQueries queries at a
@@ -1055,150 +1072,52 @@ constexpr int kRankPassQueries = 32768;
 int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, uint32_t flags,
                   const int64_t* t_ptr, const uint32_t* t_ord, const int32_t* self_ord, uint32_t* out_rank,
                   uint32_t* out_score_u32, float ms[2]) {
-    // ---- argument checks: no device needed
-    if (!ix || !q_ptr || !t_ptr || !out_rank || !out_score_u32 || nq < 0) {
-        set_error("msr_rank_docs: bad argument");
-        return MSR_E_INVAL;
-    }
-    if (t_ptr[0] != 0) {
-        set_error("msr_rank_docs: t_ptr must start at 0");
-        return MSR_E_INVAL;
-    }
-    for (int i = 0; i < nq; ++i)
-        if (t_ptr[i + 1] < t_ptr[i]) {
-            set_error("msr_rank_docs: t_ptr decreases at query %d", i);
-            return MSR_E_INVAL;
-        }
-    const int64_t n_ent64 = t_ptr[nq];
-    if (n_ent64 > 0 && !t_ord) {
-        set_error("msr_rank_docs: null t_ord");
-        return MSR_E_INVAL;
-    }
-    const IndexHeader* h = ix->host.h;
-    if (ix->term_nshards > 0 || ix->shard_ntiles != h->n_tiles) {
-        set_error("msr_rank_docs: a rank counts over every doc and every term; this handle is a %s shard (open the whole "
-                  "index with msr_index_open)", ix->term_nshards > 0 ? "term-range" : "doc-range");
-        return MSR_E_INVAL;
-    }
-    for (int i = 0; i < nq; ++i) {
-        if (t_ptr[i + 1] - t_ptr[i] > MSR_RANK_MAX_TARGETS) {
-            set_error("msr_rank_docs: query %d lists %lld docs (at most MSR_RANK_MAX_TARGETS = %d)", i,
-                      (long long)(t_ptr[i + 1] - t_ptr[i]), MSR_RANK_MAX_TARGETS);
-            return MSR_E_RANGE;
-        }
-        if (self_ord && self_ord[i] >= 0 && (uint64_t)self_ord[i] >= h->n_docs) {
-            set_error("msr_rank_docs: self_ord[%d] = %d is outside the index (%llu docs)", i, self_ord[i],
-                      (unsigned long long)h->n_docs);
-            return MSR_E_RANGE;
-        }
-    }
-    for (int64_t e = 0; e < n_ent64; ++e)
-        if ((uint64_t)t_ord[e] >= h->n_docs) {
-            set_error("msr_rank_docs: ordinal %u (entry %lld) is outside the index (%llu docs)", t_ord[e], (long long)e,
-                      (unsigned long long)h->n_docs);
-            return MSR_E_RANGE;
-        }
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
-        return MSR_E_NODEVICE;
-    }
+    const char* const who = "msr_rank_docs";
+    // ---- checks
+    int rc = listed_check_shapes(who, ix, ix && q_ptr && t_ptr && out_rank && out_score_u32 && nq >= 0, nq, t_ptr, t_ord);
+    if (rc == MSR_OK) rc = listed_check_ranges(who, ix, nq, t_ptr, t_ord, self_ord, MSR_RANK_MAX_TARGETS, "MSR_RANK_MAX_TARGETS");
+    if (rc != MSR_OK) return rc;
     if (ms) ms[0] = ms[1] = 0.f;
+    const int64_t n_ent64 = t_ptr[nq];
     if (nq == 0 || n_ent64 == 0) return MSR_OK;
     if ((uint64_t)n_ent64 + (uint64_t)nq > 0xFFFFFFF0ull) {
-        set_error("msr_rank_docs: too many listed docs");
+        set_error("%s: too many listed docs", who);
         return MSR_E_RANGE;
     }
     const uint32_t n_ent = (uint32_t)n_ent64;
+    const uint32_t tile = ix->host.h->tile_docs, n_tiles = ix->host.h->n_tiles;
     DeviceIndex* d = ix->dev;
-    // ---- the queries, normalised and uploaded exactly as for a search (refusals included)
+    // the queries, normalised and uploaded exactly as for a search (refusals included)
     msr_batch* b = nullptr;
-    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
+    rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
     if (rc != MSR_OK) return rc;
-    // ---- (query, tile) pairs that hold a listed doc or the query's self doc, tile-major; the docs of a pair
-    const uint32_t tile = h->tile_docs, n_tiles = h->n_tiles;
-    struct Item {
-        uint32_t tile, q, slot, local;
-    };
-    std::vector<Item> its;
-    its.reserve((size_t)n_ent + (size_t)nq);
-    for (int i = 0; i < nq; ++i) {
-        for (int64_t e = t_ptr[i]; e < t_ptr[i + 1]; ++e)
-            its.push_back({t_ord[e] / tile, (uint32_t)i, (uint32_t)e, t_ord[e] % tile});
-        if (self_ord && self_ord[i] >= 0)
-            its.push_back({(uint32_t)self_ord[i] / tile, (uint32_t)i, n_ent + (uint32_t)i, (uint32_t)self_ord[i] % tile});
-    }
-    std::stable_sort(its.begin(), its.end(), [](const Item& x, const Item& y) { return x.tile != y.tile ? x.tile < y.tile : x.q < y.q; });
-    // one upload block: t_ptr | t_ord | entry -> query | self | pairs (uint4) | items (uint2)
-    auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-    std::vector<uint32_t> pairs;
-    pairs.reserve(its.size() * 4);
-    for (size_t i = 0; i < its.size(); ++i) {
-        if (i == 0 || its[i].tile != its[i - 1].tile || its[i].q != its[i - 1].q) {
-            const uint32_t row[4] = {its[i].q, its[i].tile, (uint32_t)i, 0u};
-            pairs.insert(pairs.end(), row, row + 4);
-        }
-        ++pairs[pairs.size() - 1];
-    }
-    const uint32_t n_pairs = (uint32_t)(pairs.size() / 4);
-    const size_t o_tp = 0, o_to = o_tp + al((size_t)nq + 1), o_eq = o_to + al(n_ent), o_self = o_eq + al(n_ent),
-                 o_pairs = o_self + al((size_t)nq), o_items = o_pairs + al(pairs.size()), in_words = o_items + al(its.size() * 2);
-    std::vector<uint32_t> blk(in_words, 0u);
-    for (int i = 0; i <= nq; ++i) blk[o_tp + (size_t)i] = (uint32_t)t_ptr[i];
-    memcpy(blk.data() + o_to, t_ord, (size_t)n_ent * 4);
-    for (int i = 0; i < nq; ++i) {
-        for (int64_t e = t_ptr[i]; e < t_ptr[i + 1]; ++e) blk[o_eq + (size_t)e] = (uint32_t)i;
-        blk[o_self + (size_t)i] = (self_ord && self_ord[i] >= 0) ? (uint32_t)self_ord[i] : kRankNoSelf;
-    }
-    memcpy(blk.data() + o_pairs, pairs.data(), pairs.size() * 4);
-    for (size_t i = 0; i < its.size(); ++i) {
-        blk[o_items + 2 * i] = its[i].slot;
-        blk[o_items + 2 * i + 1] = its[i].local;
-    }
+    CallScratch cs(d, b);
+    // ---- plan: (query, tile) pairs that hold a listed doc or the query's self doc, tile-major; the docs of a pair
+    RankPlan pl;
+    rank_plan(tile, nq, t_ptr, t_ord, self_ord, pl);
+    const uint32_t n_pairs = (uint32_t)(pl.pairs.size() / 4);
+    // ---- upload, one block: t_ptr | t_ord | entry -> query | self | pairs (uint4) | items (uint2)
+    const size_t o_tp = cs.put(pl.t_ptr), o_to = cs.put(t_ord, n_ent), o_eq = cs.put(pl.e_query), o_self = cs.put(pl.self),
+                 o_pairs = cs.put(pl.pairs), o_items = cs.put(pl.items);
     // passes of the count phase and the scratch of the largest one
     uint32_t max_pe = 0;
     for (int q0 = 0; q0 < nq; q0 += kRankPassQueries)
         max_pe = std::max<uint32_t>(max_pe, (uint32_t)(t_ptr[std::min(nq, q0 + kRankPassQueries)] - t_ptr[q0]));
-    const size_t in_bytes = in_words * 4, sc_bytes = ((size_t)n_ent + (size_t)nq) * 4, rk_bytes = (size_t)n_ent * 4,
+    const size_t in_bytes = cs.in.size() * 4, sc_bytes = ((size_t)n_ent + (size_t)nq) * 4, rk_bytes = (size_t)n_ent * 4,
                  part_bytes = std::max<size_t>((size_t)n_tiles * max_pe, 1) * 4;
-    uint32_t* d_in = (uint32_t*)d->pool.alloc(in_bytes);
-    uint32_t* d_sc = (uint32_t*)d->pool.alloc(sc_bytes);
-    uint32_t* d_rk = (uint32_t*)d->pool.alloc(rk_bytes);
-    uint32_t* d_part = (uint32_t*)d->pool.alloc(part_bytes);
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto done = [&](int r) {
-        if (r != MSR_OK) (void)hipStreamSynchronize(d->stream);  // nothing in flight may still use the scratch
-        d->pool.release(d_in, in_bytes);
-        d->pool.release(d_sc, sc_bytes);
-        d->pool.release(d_rk, rk_bytes);
-        d->pool.release(d_part, part_bytes);
-        for (hipEvent_t e : ev) {
-            if (!e) continue;
-            if (d->spare_events.size() < 64)
-                d->spare_events.push_back(e);
-            else
-                (void)hipEventDestroy(e);
-        }
-        batch_free(b);
-        return r;
-    };
+    uint32_t *d_in = cs.alloc(in_bytes), *d_sc = cs.alloc(sc_bytes), *d_rk = cs.alloc(rk_bytes), *d_part = cs.alloc(part_bytes);
     if (!d_in || !d_sc || !d_rk || !d_part) {
-        set_error("msr_rank_docs: device allocation failed (%zu bytes of per-tile counts)", part_bytes);
-        return done(MSR_E_NOMEM);
+        set_error("%s: device allocation failed (%zu bytes of per-tile counts)", who, part_bytes);
+        return MSR_E_NOMEM;
     }
-    auto try_hip = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        set_error("msr_rank_docs: %s failed: %s", what, hipGetErrorString(e));
-        return false;
-    };
-    if (!try_hip(hipMemcpy(d_in, blk.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return done(MSR_E_HIP);
-    for (int i = 0; ms && i < 3; ++i) {
-        if (!d->spare_events.empty()) {
-            ev[i] = d->spare_events.back();
-            d->spare_events.pop_back();
-        } else if (!try_hip(hipEventCreate(&ev[i]), "hipEventCreate")) {
-            return done(MSR_E_HIP);
+    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return MSR_E_HIP;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; ms && i < 3; ++i)
+        if (!(ev[i] = cs.event())) {
+            set_error("%s: hipEventCreate failed", who);
+            return MSR_E_HIP;
         }
-    }
+    // ---- launches: the gather over the pairs, then count + reduce per pass of queries
     RankArgs ra;
     fill_score_args(ra.s, b, 1);
     ra.s.light = b->max_sparse_terms <= 64 ? 1u : 0u;
@@ -1216,10 +1135,10 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
     ra.e0 = 0;
     ra.pe = 0;
     ra.n_tiles = n_tiles;
-    if (ms && !try_hip(hipEventRecord(ev[0], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
     rc = launch_rank(d->stream, tile, false, n_pairs, 0, ra);
-    if (rc != MSR_OK) return done(rc);
-    if (ms && !try_hip(hipEventRecord(ev[1], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
+    if (rc != MSR_OK) return rc;
+    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
     for (int q0 = 0; q0 < nq; q0 += kRankPassQueries) {
         const int q1 = std::min(nq, q0 + kRankPassQueries);
         ra.s.q0 = (uint32_t)q0;
@@ -1228,61 +1147,42 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
         ra.pe = (uint32_t)(t_ptr[q1] - t_ptr[q0]);
         if (ra.pe == 0) continue;
         rc = launch_rank(d->stream, tile, true, 0, n_tiles, ra);
-        if (rc != MSR_OK) return done(rc);
+        if (rc != MSR_OK) return rc;
         hipLaunchKernelGGL(rank_reduce, dim3((ra.pe + 255) / 256), dim3(256), 0, d->stream, ra);
-        if (!try_hip(hipGetLastError(), "rank_reduce")) return done(MSR_E_HIP);
+        if (!hip_ok(who, hipGetLastError(), "rank_reduce")) return MSR_E_HIP;
     }
-    if (ms && !try_hip(hipEventRecord(ev[2], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
-    if (!try_hip(hipStreamSynchronize(d->stream), "the rank kernels")) return done(MSR_E_HIP);
-    if (!try_hip(hipMemcpy(out_rank, d_rk, rk_bytes, hipMemcpyDeviceToHost), "download") ||
-        !try_hip(hipMemcpy(out_score_u32, d_sc, (size_t)n_ent * 4, hipMemcpyDeviceToHost), "download"))
-        return done(MSR_E_HIP);
-    if (ms && (!try_hip(hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
-               !try_hip(hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
-        return done(MSR_E_HIP);
-    return done(MSR_OK);
+    if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    // ---- download
+    if (!hip_ok(who, hipStreamSynchronize(d->stream), "the rank kernels") ||
+        !hip_ok(who, hipMemcpy(out_rank, d_rk, rk_bytes, hipMemcpyDeviceToHost), "download") ||
+        !hip_ok(who, hipMemcpy(out_score_u32, d_sc, (size_t)n_ent * 4, hipMemcpyDeviceToHost), "download"))
+        return MSR_E_HIP;
+    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
+               !hip_ok(who, hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
+        return MSR_E_HIP;
+    cs.ok = true;
+    return MSR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ explain listed docs
 int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq,
                      uint32_t flags, const int64_t* t_ptr, const uint32_t* t_ord, uint32_t* out_doc_w, int64_t out_cap,
                      float ms[1]) {
-    // ---- argument checks: no device needed
-    if (!ix || !q_ptr || !t_ptr || !out_doc_w || nq < 0) {
-        set_error("msr_explain_docs: bad argument");
-        return MSR_E_INVAL;
-    }
-    if (t_ptr[0] != 0) {
-        set_error("msr_explain_docs: t_ptr must start at 0");
-        return MSR_E_INVAL;
-    }
-    for (int i = 0; i < nq; ++i)
-        if (t_ptr[i + 1] < t_ptr[i]) {
-            set_error("msr_explain_docs: t_ptr decreases at query %d", i);
-            return MSR_E_INVAL;
-        }
-    const int64_t n_ent64 = t_ptr[nq];
-    if (n_ent64 > 0 && !t_ord) {
-        set_error("msr_explain_docs: null t_ord");
-        return MSR_E_INVAL;
-    }
+    const char* const who = "msr_explain_docs";
+    // ---- checks: the query rows and the output's size come between the shared shapes and the shared ranges
+    int rc = listed_check_shapes(who, ix, ix && q_ptr && t_ptr && out_doc_w && nq >= 0, nq, t_ptr, t_ord);
+    if (rc != MSR_OK) return rc;
     if (q_ptr[0] < 0) {
-        set_error("msr_explain_docs: q_ptr is negative");
+        set_error("%s: q_ptr is negative", who);
         return MSR_E_INVAL;
     }
     for (int i = 0; i < nq; ++i)
         if (q_ptr[i + 1] < q_ptr[i]) {
-            set_error("msr_explain_docs: q_ptr is not monotone at query %d", i);
+            set_error("%s: q_ptr is not monotone at query %d", who, i);
             return MSR_E_INVAL;
         }
     if (q_ptr[nq] > 0 && (!q_term || !q_w)) {
-        set_error("msr_explain_docs: bad CSR arrays");
-        return MSR_E_INVAL;
-    }
-    const IndexHeader* h = ix->host.h;
-    if (ix->term_nshards > 0 || ix->shard_ntiles != h->n_tiles) {
-        set_error("msr_explain_docs: the weights of a doc lie in every term's segments of its tile; this handle is a %s "
-                  "shard (open the whole index with msr_index_open)", ix->term_nshards > 0 ? "term-range" : "doc-range");
+        set_error("%s: bad CSR arrays", who);
         return MSR_E_INVAL;
     }
     uint64_t need = 0;  // u32 slots of the ragged output (saturating)
@@ -1292,95 +1192,47 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
         need = std::min<uint64_t>((uint64_t)INT64_MAX, need + add);
     }
     if (out_cap < 0 || (uint64_t)out_cap < need) {
-        set_error("msr_explain_docs: out_cap = %lld is below the %llu slots the listed docs own", (long long)out_cap,
+        set_error("%s: out_cap = %lld is below the %llu slots the listed docs own", who, (long long)out_cap,
                   (unsigned long long)need);
         return MSR_E_INVAL;
     }
-    for (int i = 0; i < nq; ++i)
-        if (t_ptr[i + 1] - t_ptr[i] > MSR_EXPLAIN_MAX_TARGETS) {
-            set_error("msr_explain_docs: query %d lists %lld docs (at most MSR_EXPLAIN_MAX_TARGETS = %d)", i,
-                      (long long)(t_ptr[i + 1] - t_ptr[i]), MSR_EXPLAIN_MAX_TARGETS);
-            return MSR_E_RANGE;
-        }
-    for (int64_t e = 0; e < n_ent64; ++e)
-        if ((uint64_t)t_ord[e] >= h->n_docs) {
-            set_error("msr_explain_docs: ordinal %u (entry %lld) is outside the index (%llu docs)", t_ord[e], (long long)e,
-                      (unsigned long long)h->n_docs);
-            return MSR_E_RANGE;
-        }
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
-        return MSR_E_NODEVICE;
-    }
+    rc = listed_check_ranges(who, ix, nq, t_ptr, t_ord, nullptr, MSR_EXPLAIN_MAX_TARGETS, "MSR_EXPLAIN_MAX_TARGETS");
+    if (rc != MSR_OK) return rc;
     if (ms) ms[0] = 0.f;
-    if (nq == 0 || n_ent64 == 0 || need == 0) return MSR_OK;
+    if (nq == 0 || t_ptr[nq] == 0 || need == 0) return MSR_OK;
     if (need > 0xFFFFFFF0ull) {
-        set_error("msr_explain_docs: the listed docs own %llu output slots, more than one call serves (split the batch)",
+        set_error("%s: the listed docs own %llu output slots, more than one call serves (split the batch)", who,
                   (unsigned long long)need);
         return MSR_E_RANGE;
     }
     DeviceIndex* d = ix->dev;
-    // ---- the search path's normalisation, run for its refusals only (MSR_E_OVERFLOW / MSR_E_RANGE, term ids checked):
-    // the kernel below reads none of the batch's arrays
+    // the search path's normalisation, run for its refusals only (MSR_E_OVERFLOW / MSR_E_RANGE, term ids checked): the
+    // kernel below reads none of the batch's arrays
     msr_batch* b = nullptr;
-    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
+    rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
     if (rc != MSR_OK) return rc;
-    // ---- the tables the kernel reads (msr_explain_plan.hpp: plain host code). A repeated target of a query is listed
-    // once; its row is copied below, after the download
-    const uint32_t tile = h->tile_docs;
+    CallScratch cs(d, b);
+    // ---- plan: the tables the kernel reads. A repeated target of a query is listed once; its row is copied below,
+    // after the download
     ExplainPlan pl;
     explain_plan(ix->host, q_ptr, q_term, q_w, nq, flags, t_ptr, t_ord, pl);
-    const std::vector<uint32_t>&qr = pl.q_range, &ents = pl.ents, &pairs = pl.pairs, &x_off = pl.x_off;
-    const std::vector<ExplainPlan::Item>& its = pl.items;
-    const uint32_t n_pairs = (uint32_t)(pairs.size() / 4);
-    // one upload block: pairs (uint4) | items (uint2) | entry ranges (uint2) | entries (uint2)
-    auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-    const size_t o_pairs = 0, o_items = o_pairs + al(pairs.size()), o_qr = o_items + al(its.size() * 2),
-                 o_ents = o_qr + al(qr.size()), in_words = o_ents + al(ents.size());
-    std::vector<uint32_t> blk(std::max<size_t>(in_words, 1), 0u);
-    if (!pairs.empty()) memcpy(blk.data() + o_pairs, pairs.data(), pairs.size() * 4);
-    for (size_t i = 0; i < its.size(); ++i) {
-        blk[o_items + 2 * i] = its[i].row;
-        blk[o_items + 2 * i + 1] = its[i].local;
-    }
-    memcpy(blk.data() + o_qr, qr.data(), qr.size() * 4);
-    if (!ents.empty()) memcpy(blk.data() + o_ents, ents.data(), ents.size() * 4);
-    const size_t in_bytes = blk.size() * 4, out_bytes = (size_t)need * 4;
-    uint32_t* d_in = (uint32_t*)d->pool.alloc(in_bytes);
-    uint32_t* d_out = (uint32_t*)d->pool.alloc(out_bytes);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto done = [&](int r) {
-        if (r != MSR_OK) (void)hipStreamSynchronize(d->stream);  // nothing in flight may still use the scratch
-        d->pool.release(d_in, in_bytes);
-        d->pool.release(d_out, out_bytes);
-        for (hipEvent_t e : ev) {
-            if (!e) continue;
-            if (d->spare_events.size() < 64)
-                d->spare_events.push_back(e);
-            else
-                (void)hipEventDestroy(e);
-        }
-        batch_free(b);
-        return r;
-    };
+    const uint32_t n_pairs = (uint32_t)(pl.pairs.size() / 4);
+    // ---- upload, one block: pairs (uint4) | items (uint2) | entry ranges (uint2) | entries (uint2)
+    const size_t o_pairs = cs.put(pl.pairs), o_items = cs.put(pl.items), o_qr = cs.put(pl.q_range), o_ents = cs.put(pl.ents);
+    const size_t in_bytes = cs.in.size() * 4, out_bytes = (size_t)need * 4;
+    uint32_t *d_in = cs.alloc(in_bytes), *d_out = cs.alloc(out_bytes);
     if (!d_in || !d_out) {
-        set_error("msr_explain_docs: device allocation failed (%zu bytes of doc weights)", out_bytes);
-        return done(MSR_E_NOMEM);
+        set_error("%s: device allocation failed (%zu bytes of doc weights)", who, out_bytes);
+        return MSR_E_NOMEM;
     }
-    auto try_hip = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        set_error("msr_explain_docs: %s failed: %s", what, hipGetErrorString(e));
-        return false;
-    };
-    if (!try_hip(hipMemcpy(d_in, blk.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return done(MSR_E_HIP);
-    for (int i = 0; ms && i < 2; ++i) {
-        if (!d->spare_events.empty()) {
-            ev[i] = d->spare_events.back();
-            d->spare_events.pop_back();
-        } else if (!try_hip(hipEventCreate(&ev[i]), "hipEventCreate")) {
-            return done(MSR_E_HIP);
+    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return MSR_E_HIP;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (int i = 0; ms && i < 2; ++i)
+        if (!(ev[i] = cs.event())) {
+            set_error("%s: hipEventCreate failed", who);
+            return MSR_E_HIP;
         }
-    }
+    // ---- launches: the output zeroed, then explain_tiles over the pairs
     ExplainArgs xa;
     xa.seg_ptr = d->d_seg_ptr;
     xa.postings = d->d_postings;
@@ -1393,19 +1245,22 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
     xa.q_range = reinterpret_cast<const uint2*>(d_in + o_qr);
     xa.ents = reinterpret_cast<const uint2*>(d_in + o_ents);
     xa.out = d_out;
-    if (ms && !try_hip(hipEventRecord(ev[0], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
-    if (!try_hip(hipMemsetAsync(d_out, 0, out_bytes, d->stream), "hipMemsetAsync")) return done(MSR_E_HIP);
-    rc = launch_explain(d->stream, tile, n_pairs, xa);
-    if (rc != MSR_OK) return done(rc);
-    if (ms && !try_hip(hipEventRecord(ev[1], d->stream), "hipEventRecord")) return done(MSR_E_HIP);
-    if (!try_hip(hipStreamSynchronize(d->stream), "the explain kernel")) return done(MSR_E_HIP);
-    if (!try_hip(hipMemcpy(out_doc_w, d_out, out_bytes, hipMemcpyDeviceToHost), "download")) return done(MSR_E_HIP);
-    if (ms && !try_hip(hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime")) return done(MSR_E_HIP);
+    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if (!hip_ok(who, hipMemsetAsync(d_out, 0, out_bytes, d->stream), "hipMemsetAsync")) return MSR_E_HIP;
+    rc = launch_explain(d->stream, ix->host.h->tile_docs, n_pairs, xa);
+    if (rc != MSR_OK) return rc;
+    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    // ---- download
+    if (!hip_ok(who, hipStreamSynchronize(d->stream), "the explain kernel") ||
+        !hip_ok(who, hipMemcpy(out_doc_w, d_out, out_bytes, hipMemcpyDeviceToHost), "download"))
+        return MSR_E_HIP;
+    if (ms && !hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime")) return MSR_E_HIP;
     for (const auto& dp : pl.dups) {  // a repeated target: the row of the entry it repeats
         const uint32_t q = (uint32_t)(std::upper_bound(t_ptr, t_ptr + nq + 1, (int64_t)dp.first) - t_ptr - 1);
-        memcpy(out_doc_w + x_off[dp.first], out_doc_w + x_off[dp.second], (size_t)(q_ptr[q + 1] - q_ptr[q]) * 4);
+        memcpy(out_doc_w + pl.x_off[dp.first], out_doc_w + pl.x_off[dp.second], (size_t)(q_ptr[q + 1] - q_ptr[q]) * 4);
     }
-    return done(MSR_OK);
+    cs.ok = true;
+    return MSR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ merge of host lists
@@ -1666,17 +1521,7 @@ int msr_batch_search_termshard(msr_batch* b, int k) {
     if (rc == MSR_OK)
         rc = ensure_buf((void**)&b->d_tpart, &b->tpart_elems, (size_t)p.tpr * b->nq * b->kmax, 8, "the per-tile keys");
     if (rc != MSR_OK) return rc;
-    if (b->calls >= 4096) b->calls = 0;
-    while (b->events.size() < (b->calls + 1) * 3) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        b->events.push_back(e);
-    }
-    b->ev0 = b->events[b->calls * 3 + 0];
-    b->ev1 = b->events[b->calls * 3 + 1];
-    b->ev2 = b->events[b->calls * 3 + 2];
-    b->calls++;
-    HIP_TRY(hipEventRecord(b->ev0, d->stream));
+    if (int rc0 = batch_begin_timed(b)) return rc0;
     for (uint32_t q0 = 0; q0 < (uint32_t)b->nq; q0 += p.qt) {
         const uint32_t qn = std::min<uint32_t>(p.qt, (uint32_t)b->nq - q0);
         const size_t send = (size_t)qn * p.range_elems * p.G;

@@ -35,6 +35,48 @@ constexpr uint32_t kSmallMaxPairs = 1024;     // a small call launches at most t
 constexpr int kChunkVecs = 64;   // one chunk = one wave-wide uint4 load = 256 postings = 1 KiB
 static_assert(kCandCap >= MSR_KMAX, "candidate buffer must hold k keys");
 
+// ------------------------------------------------------------------------------------------------ tile shapes
+// The launch shape of every kernel that works on one doc tile: <tile, threads, chunk loads per bank, min waves/SIMD of
+// the k <= 512 instance, of the other instances>. `light` marks the small tiles: only they have a light scorer
+// (score_tiles<..., LIGHT>) and the hybrid kernels (hybrid_tiles, fuse_tiles).
+template <uint32_t DOCS, uint32_t THREADS, uint32_t LOADS, uint32_t WAVES, uint32_t WAVES_REST>
+struct TileShape {
+    static constexpr uint32_t docs = DOCS, threads = THREADS, loads = LOADS, waves = WAVES, waves_rest = WAVES_REST;
+    static constexpr bool light = DOCS == 4096 || DOCS == 8192;
+};
+
+// Calls f(TileShape<...>{}) for the shape of `tile_docs`; false: no such shape. THE table: every launcher goes through it.
+template <class F>
+inline bool with_tile_shape(uint32_t tile_docs, F&& f) {
+    // LDS per workgroup = 4 B x tile + 4-8 KiB candidates + maxima -> workgroups (waves) per CU:
+    switch (tile_docs) {
+        case 32768: f(TileShape<32768, 1024, 8, 4, 4>{}); return true;  // 1 (16)
+        case 16384: f(TileShape<16384, 512, 8, 4, 4>{}); return true;   // 2 (16)
+        case 12288: f(TileShape<12288, 512, 4, 4, 4>{}); return true;   // 2 (16)
+        case 8192: f(TileShape<8192, 512, 4, 8, 6>{}); return true;     // 4 (32) with k <= 512, 3 (24) above
+        case 4096: f(TileShape<4096, 256, 4, 6, 5>{}); return true;     // 7 (28)
+        default: return false;
+    }
+}
+
+// device_attach refuses an index whose tile size has no shape, so the launchers never get here with an open handle
+inline int no_tile_shape(uint32_t tile_docs) {
+    set_error("no kernel instance for tile_docs=%u (supported: 4096, 8192, 12288, 16384, 32768)", tile_docs);
+    return MSR_E_RANGE;
+}
+
+inline uint32_t tile_threads(uint32_t tile_docs) {  // of the tile's scoring and selection instances (0: no such shape)
+    uint32_t n = 0;
+    with_tile_shape(tile_docs, [&](auto s) { n = s.threads; });
+    return n;
+}
+
+inline bool hybrid_tile(uint32_t tile_docs) {  // the tile sizes the hybrid kernels are instantiated for
+    bool yes = false;
+    with_tile_shape(tile_docs, [&](auto s) { yes = s.light; });
+    return yes;
+}
+
 // Caching device allocator of one index handle. msr_search_csr at the reference's call shape (4 queries per call,
 // scripts/search_sparse.sh:16) would otherwise spend more time in hipMalloc / hipFree than in its kernels.
 struct DevicePool {
@@ -81,7 +123,7 @@ struct DeviceIndex {
     int device = -1;
     hipStream_t stream = nullptr;
     DevicePool pool;
-    std::vector<hipEvent_t> spare_events;  // recycled by the batches of this handle
+    std::vector<hipEvent_t> spare_events;  // recycled by the calls on this handle: borrow_event / return_event only
     void* h_stage = nullptr;               // pinned staging for small uploads / downloads
     size_t h_stage_bytes = 0;
     hipEvent_t stage_ev = nullptr;         // recorded after an async upload out of h_stage ...
@@ -106,7 +148,33 @@ struct DeviceIndex {
     ncclComm_t comm = nullptr;
     int n_ranks = 1;
     int rank = 0;
+
+    // a timing event: a spare one, else a new one (null: hipEventCreate failed); handed back, at most 64 are kept
+    hipEvent_t borrow_event() {
+        hipEvent_t e = nullptr;
+        if (!spare_events.empty()) {
+            e = spare_events.back();
+            spare_events.pop_back();
+        } else if (hipEventCreate(&e) != hipSuccess) {
+            e = nullptr;
+        }
+        return e;
+    }
+    void return_event(hipEvent_t e) {
+        if (!e) return;
+        if (spare_events.size() < 64)
+            spare_events.push_back(e);
+        else
+            (void)hipEventDestroy(e);
+    }
 };
+
+// false, with the error set to "<who>: <what> failed: <HIP's words>", unless e is hipSuccess
+inline bool hip_ok(const char* who, hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    set_error("%s: %s failed: %s", who, what, hipGetErrorString(e));
+    return false;
+}
 
 // ------------------------------------------------------------------------------------------------ kernel arguments
 struct ScoreArgs {
@@ -210,3 +278,41 @@ void batch_free(msr_batch* b);          // release + unregister from the index +
 void batch_release_device(msr_batch* b); // device buffers and events only (the index is being closed)
 extern "C" int batch_search_local(msr_batch* b, int k, bool final_arrays);  // internal, not part of include/msr.h
 void fill_score_args(msr::ScoreArgs& sa, msr_batch* b, int k);  // a launch over the whole batch and every tile
+
+// The device scratch of one call on a handle: the pool blocks it handed out, the events it borrowed and (optionally) the
+// call's batch. Leaving the scope waits for the stream unless the call set `ok` (nothing in flight may still use the
+// scratch), then gives the blocks back to the pool, the events back to the handle and frees the batch, in this order.
+struct CallScratch {
+    msr::DeviceIndex* d;
+    msr_batch* b;
+    bool ok = false;  // the call succeeded: its last step waited for the stream already
+    std::vector<std::pair<void*, size_t>> blocks;
+    std::vector<hipEvent_t> events;
+    explicit CallScratch(msr::DeviceIndex* dev, msr_batch* batch = nullptr) : d(dev), b(batch) {}
+    CallScratch(const CallScratch&) = delete;
+    CallScratch& operator=(const CallScratch&) = delete;
+    ~CallScratch() {
+        if (!ok) (void)hipStreamSynchronize(d->stream);
+        for (auto& blk : blocks) d->pool.release(blk.first, blk.second);
+        for (hipEvent_t e : events) d->return_event(e);
+        batch_free(b);
+    }
+    std::vector<uint32_t> in;  // the call's upload block: u32 sub-buffers, each starting on a 256-byte boundary
+    size_t put(const uint32_t* src, size_t n) {  // appends a sub-buffer of n words; its first word
+        const size_t at = in.size();
+        in.resize(at + (n + 63) / 64 * 64, 0u);
+        if (n) memcpy(in.data() + at, src, n * 4);
+        return at;
+    }
+    size_t put(const std::vector<uint32_t>& v) { return put(v.data(), v.size()); }
+    uint32_t* alloc(size_t bytes) {  // null: out of device memory
+        void* p = d->pool.alloc(bytes);
+        if (p) blocks.emplace_back(p, bytes);
+        return (uint32_t*)p;
+    }
+    hipEvent_t event() {  // null: hipEventCreate failed
+        hipEvent_t e = d->borrow_event();
+        if (e) events.push_back(e);
+        return e;
+    }
+};

@@ -23,7 +23,7 @@
 //                 and of terms the doc lacks are never written.
 #pragma once
 
-#include "msr_explain_plan.hpp"
+#include "msr_listed_plan.hpp"
 #include "msr_select.hpp"
 
 namespace msr {

@@ -1603,6 +1603,16 @@ static int hybrid_download(const HybridArgs& ha, int nq, int k, uint32_t* out_or
     return MSR_OK;
 }
 
+// hybrid_tiles<MODE> at the tile's launch shape (1024 candidate keys: waves_rest); only the `light` shapes have one
+template <int MODE>
+static void launch_hybrid_tiles(uint32_t tile_docs, dim3 grid, hipStream_t st, const ScoreArgs& sa, const HybridArgs& ha) {
+    with_tile_shape(tile_docs, [&](auto sh) {
+        using S = decltype(sh);
+        if constexpr (S::light)
+            hipLaunchKernelGGL((hybrid_tiles<S::docs, S::threads, S::loads, S::waves_rest, MODE>), grid, dim3(S::threads), 0, st, sa, ha);
+    });
+}
+
 // The fused path of msr_hybrid_search (single-tile indexes, k <= 64): per chunk of queries (normally ONE chunk) a GEMM
 // launch on the ordinal-permuted passage matrix, then hybrid_tiles. ms = {fused scoring + selection + fusion kernel, dense GEMM, 0, 0}.
 static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
@@ -1613,7 +1623,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
     const IndexHeader* h = ix->host.h;
     const uint64_t n = h->n_docs;
     HIP_TRY(hipSetDevice(d->device));
-    const uint32_t nt_threads = h->tile_docs == 4096 ? 256u : 512u;
+    const uint32_t nt_threads = tile_threads(h->tile_docs);
     const uint64_t ld = (n + 4 * nt_threads - 1) / (4 * nt_threads) * (4 * nt_threads);  // whole select rounds
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (n + 255) / 256 * 256);
     const uint32_t gb = hybrid_gemm_block(dx);  // 256 x 256 fp16 blocks, 128 x 128 f32 blocks
@@ -1655,10 +1665,7 @@ static int hybrid_search_fused(msr_index* ix, msr_dense* dx, const int64_t* q_pt
         (void)hipEventRecord(e[1], d->stream);
         sa.q0 = q0;
         sa.qn = qn;
-        if (h->tile_docs == 4096)
-            hipLaunchKernelGGL((hybrid_tiles<4096, 256, 4, 5>), dim3(qn), dim3(256), 0, d->stream, sa, ha);
-        else
-            hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6>), dim3(qn), dim3(512), 0, d->stream, sa, ha);
+        launch_hybrid_tiles<0>(h->tile_docs, dim3(qn), d->stream, sa, ha);
         if (hipGetLastError() != hipSuccess) {
             set_error("hybrid_tiles launch failed: %s", hipGetErrorString(hipGetLastError()));
             rc = MSR_E_HIP;
@@ -1798,10 +1805,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
                 return MSR_E_RANGE;
             }
             const dim3 grid(rows, n_tiles);
-            if (tile == 4096)
-                hipLaunchKernelGGL((hybrid_tiles<4096, 256, 4, 5, 1>), grid, dim3(256), 0, d->stream, sa, ha);
-            else
-                hipLaunchKernelGGL((hybrid_tiles<8192, 512, 4, 6, 1>), grid, dim3(512), 0, d->stream, sa, ha);
+            launch_hybrid_tiles<1>(tile, grid, d->stream, sa, ha);
         }
         if (hipGetLastError() != hipSuccess) {
             set_error("hybrid_tiles launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1828,19 +1832,12 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     std::vector<hipEvent_t> ev;
     auto four_events = [&]() -> hipEvent_t* {
         const size_t at = ev.size();
+        bool all = true;
         for (int i = 0; i < 4; ++i) {
-            hipEvent_t x = nullptr;
-            if (!d->spare_events.empty()) {
-                x = d->spare_events.back();
-                d->spare_events.pop_back();
-            } else if (hipEventCreate(&x) != hipSuccess) {
-                x = nullptr;
-            }
-            ev.push_back(x);
+            ev.push_back(d->borrow_event());
+            all = all && ev.back();
         }
-        for (size_t i = at; i < ev.size(); ++i)
-            if (!ev[i]) return nullptr;
-        return ev.data() + at;
+        return all ? ev.data() + at : nullptr;
     };
     ev.reserve(4 * ((size_t)nq / std::max<uint32_t>(qc, 1) + 4) + 64);  // (pointers into ev stay valid)
     for (uint32_t q0 = 0; q0 < (uint32_t)nq && rc == MSR_OK; q0 += qc) {
@@ -1928,13 +1925,7 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
         ms[2] = 0.f;
         ms[3] = t_fuse;
     }
-    for (hipEvent_t x : ev) {
-        if (!x) continue;
-        if (d->spare_events.size() < 64)
-            d->spare_events.push_back(x);
-        else
-            (void)hipEventDestroy(x);
-    }
+    for (hipEvent_t x : ev) d->return_event(x);
     batch_free(s.b);
     return rc;
 }
@@ -1971,11 +1962,11 @@ static int hybrid_search_impl(const char* fn, msr_index* ix, msr_dense* dx, cons
     // (permute_rows moves uint4: an fp16 row needs h % 8 == 0; an f32 row of hp floats always qualifies)
     const bool rows_ok = dx->f32 || dx->h % 8 == 0;
     if (!no_fused && h->n_tiles == 1 && ix->shard_ntiles == 1 && ix->term_nshards == 0 && k <= 64 && rows_ok &&
-        (h->tile_docs == 4096 || h->tile_docs == 8192))
+        hybrid_tile(h->tile_docs))
         return hybrid_search_fused(ix, dx, q_ptr, q_term, q_w, q, nq, depth, k, alpha, flags, row2ord, self_ord,
                                    out_ord, out_score, out_n, ms);
     if (!no_fused && ix->shard_ntiles == h->n_tiles && ix->term_nshards == 0 && rows_ok && h->n_tiles <= kMaxGridY &&
-        (h->tile_docs == 4096 || h->tile_docs == 8192))
+        hybrid_tile(h->tile_docs))
         return hybrid_search_multitile(ix, dx, q_ptr, q_term, q_w, q, nq, depth, k, alpha, flags, row2ord, self_ord,
                                        out_ord, out_score, out_n, ms);
     msr_batch* b = nullptr;
@@ -2025,12 +2016,13 @@ static int hybrid_search_impl(const char* fn, msr_index* ix, msr_dense* dx, cons
         fa.k = (uint32_t)k;
         fa.w_dense = alpha;
         fa.w_sparse = 1.0f - alpha;
-        if (nq) {
-            if (ftile == 4096)
-                hipLaunchKernelGGL((fuse_tiles<4096, 256, 1024>), dim3(ftiles * (uint32_t)nq), dim3(256), 0, d->stream, fa);
-            else
-                hipLaunchKernelGGL((fuse_tiles<8192, 512, 1024>), dim3(ftiles * (uint32_t)nq), dim3(512), 0, d->stream, fa);
-        }
+        if (nq)
+            with_tile_shape(ftile, [&](auto sh) {
+                using S = decltype(sh);
+                if constexpr (S::light)
+                    hipLaunchKernelGGL((fuse_tiles<S::docs, S::threads, 1024>), dim3(ftiles * (uint32_t)nq), dim3(S::threads), 0,
+                                       d->stream, fa);
+            });
         MergeArgs ma;
         ma.lists = d_part;
         ma.list_stride = (uint64_t)nq * k;
@@ -2152,7 +2144,7 @@ int msr_hybrid_search_union(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, 
     const char* why = nullptr;
     if (ix->term_nshards != 0) why = "a term-range shard handle";
     else if (ix->shard_ntiles != h->n_tiles) why = "a doc-range shard handle";
-    else if (h->tile_docs != 4096 && h->tile_docs != 8192) why = "a tile size other than 4096 / 8192 docs";
+    else if (!hybrid_tile(h->tile_docs)) why = "a tile size other than 4096 / 8192 docs";
     else if (h->n_tiles > kMaxGridY) why = "more tiles than one launch holds";
     else if (!dx->f32 && dx->h % 8 != 0) why = "an fp16 dense dimension that is not a multiple of 8";
     if (why) {

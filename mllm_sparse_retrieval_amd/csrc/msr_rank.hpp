@@ -19,10 +19,9 @@
 #pragma once
 
 #include "msr_accumulate.hpp"
+#include "msr_listed_plan.hpp"
 
 namespace msr {
-
-constexpr uint32_t kRankNoSelf = 0xFFFFFFFFu;  // self[q] of a query without a self doc
 
 struct RankArgs {
     ScoreArgs s;             // what the accumulation reads (part / theta / dump are unused here)

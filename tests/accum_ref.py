@@ -10,8 +10,8 @@ numpy_scores() + rank()  int64 D @ q ranked with np.lexsort((ordinal, -score)): 
           oracle.
 
 Nothing here calls the search path of libmsr; only build() calls the index builder. When an accumulation constant
-changes (kQtBlock, kChunkVecs, UL, the MSR_LAUNCH table of launch_score), this is the file to restate it in:
-tests/test_accum_ref.py compares INSTANCES with the source text of the MSR_LAUNCH lines."""
+changes (kQtBlock, kChunkVecs, UL, the tile shapes of with_tile_shape), this is the file to restate it in:
+tests/test_accum_ref.py compares INSTANCES with the source text of the table's TileShape rows."""
 from __future__ import annotations
 
 import numpy as np
@@ -23,7 +23,7 @@ CHUNK_VECS = 64      # kChunkVecs: one chunk = 64 vecs = 256 postings = 1 KiB
 UL = 4               # accumulate_tile_light: chunk loads per wave and batch
 LIGHT_MAX = 64       # batch_search_local: the light path takes batches whose queries hold at most 64 sparse entries
 LIGHT_TILES = (4096, 8192)
-# launch_score's MSR_LAUNCH table: tile_docs -> (threads NT, chunk loads per register bank U)
+# with_tile_shape's table (msr_device_internal.hpp): tile_docs -> (threads NT, chunk loads per register bank U)
 INSTANCES = {32768: (1024, 8), 16384: (512, 8), 12288: (512, 4), 8192: (512, 4), 4096: (256, 4)}
 TILE_SIZES = sorted(INSTANCES)
 NO_TERM = 0xFFFFFFFF

@@ -1,7 +1,8 @@
 """CPU checks of tests/accum_ref.py: the planted corpora are what the built index file holds, the census of every GPU
 case list (tests/test_accum_edges.py) covers the full edge list by name, the C oracle equals the plain numpy reference
 on every planted corpus (the top-of-range ones included), and the instance table restated in the census is the one in
-the source text of launch_score. None of this needs a GPU: the index builder and the oracle are host code."""
+the source text of with_tile_shape and launch_score. None of this needs a GPU: the index builder and the oracle are
+host code."""
 import os
 import re
 
@@ -27,16 +28,23 @@ def _src(name):
 
 
 def test_instance_table_is_the_one_of_launch_score():
-    dev = _src("msr_device.hip")
-    rows = re.findall(r"case (\d+): MSR_LAUNCH\((\d+), (\d+), (\d+), \d+, \d+\)", dev)
+    dev, internal = _src("msr_device.hip"), _src("msr_device_internal.hpp")
+    # ONE table (with_tile_shape): every launcher of the two units goes through its switch
+    rows = re.findall(r"case (\d+): f\(TileShape<(\d+), (\d+), (\d+), \d+, \d+>\{\}\); return true;", internal)
     assert {int(t): (int(n), int(u)) for t, _, n, u in rows} == ar.INSTANCES and all(t == t2 for t, t2, _, _ in rows)
-    macro = dev[dev.index("#define MSR_LAUNCH"):dev.index("#undef MSR_LAUNCH")]
+    assert "static constexpr bool light = DOCS == 4096 || DOCS == 8192;" in internal and ar.LIGHT_TILES == (4096, 8192)
+    every = "".join(_src(f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp")))
+    for t in ar.INSTANCES:
+        assert every.count(f"case {t}:") == 1, t
+    rule = dev[dev.index("static int launch_score("):dev.index("int launch_select(")]
+    assert "constexpr uint32_t T = S::docs, N = S::threads, UU = S::loads, W = S::waves, WR = S::waves_rest;" in rule
     # dump / light with the 512-key buffer / k <= 512 / the 1024-key buffer, in this order
-    assert re.search(r"else if \(a\.k <= 512 && a\.light && \(T == 8192 \|\| T == 4096\)\)", macro)
-    assert re.search(r"else if \(a\.k <= 512\)\s*\\\s*hipLaunchKernelGGL\(\(score_tiles<T, N, UU, W, 512>\)", macro)
-    assert re.search(r"else\s*\\\s*hipLaunchKernelGGL\(\(score_tiles<T, N, UU, WR, 1024>\)", macro)
+    assert re.search(r"if \(dump\)\s*hipLaunchKernelGGL\(\(score_tiles<T, N, UU, WR, 512, 1>\), grid, dim3\(N\), 0, st, a\);\s*"
+                     r"else if \(a\.k <= 512 && a\.light && S::light\)\s*"
+                     r"hipLaunchKernelGGL\(\(score_tiles<T, N, UU, W, 512, 0, S::light>\), grid, dim3\(N\), 0, st, a\);\s*"
+                     r"else if \(a\.k <= 512\)\s*hipLaunchKernelGGL\(\(score_tiles<T, N, UU, W, 512>\), grid, dim3\(N\), 0, st, a\);\s*"
+                     r"else\s*hipLaunchKernelGGL\(\(score_tiles<T, N, UU, WR, 1024>\), grid, dim3\(N\), 0, st, a\);", rule)
     assert "sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;" in dev and ar.LIGHT_MAX == 64
-    internal = _src("msr_device_internal.hpp")
     assert re.search(rf"constexpr int kQtBlock = {ar.KQT_BLOCK};", internal)
     assert re.search(rf"constexpr int kChunkVecs = {ar.CHUNK_VECS};", internal)
     assert f"constexpr int UL = {ar.UL};" in _src("msr_accumulate.hpp")

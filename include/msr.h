@@ -298,6 +298,35 @@ int msr_dense_search(msr_dense* dx, const uint16_t* q_fp16, int nq, int k, uint3
 int msr_dense_open_f32(const float* p, uint64_t n, uint32_t h, int device, msr_dense** out);
 int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
                          int32_t* out_n, float* gemm_ms, float* select_ms);
+/* ---- exact ranks of listed rows on the dense route: "where does this row stand for this query", at any depth. The
+ * dense counterpart of msr_rank_docs: a flat search stops at k <= MSR_KMAX, so a judged row below that is missing from
+ * its lists and MedR / MeanR / MRR / Recall@k beyond it cannot be computed from a run. NO counterpart call in the
+ * reference, tevatron or faiss.
+ * q is [nq][h] row-major in the handle's precision: q_is_f32 = 1 for f32 rows and a handle from msr_dense_open_f32,
+ * q_is_f32 = 0 for fp16 rows and a handle from msr_dense_open; a mismatch is MSR_E_INVAL. Inputs are expected finite.
+ * The listed rows (targets) are CSR: query i owns entries [t_ptr[i], t_ptr[i+1]) of t_row (dense ROW indices; at most
+ * MSR_DENSE_RANK_MAX_TARGETS per query, duplicates allowed, none is fine). Both outputs are indexed like t_row. With
+ * key(d) the u32 key of the score this handle's GEMM gives row d for query i (the key map and the kernels of
+ * msr_dense_search / msr_dense_search_f32):
+ *     out_key  = key(t)
+ *     out_rank = 0 when t == self_row[i],
+ *                else 1 + #{ d in [0, n), d != self_row[i] : key(d) > key(t) or (key(d) == key(t) and d < t) }
+ * Every row is a hit (a flat index returns any score: there is no "score 0 = not ranked" rule), the order is by KEY (so
+ * -0 ranks below +0 exactly as the search orders them) and a score tie goes to the lower ROW, as in msr_dense_search.
+ * self_row (nullable; a negative entry = none) names the row remove_query drops (src/search.py:72-74).
+ * Link to the search: with self_row NULL and any 1 <= k <= MSR_KMAX, t is in row i of the search at k exactly when
+ * rank <= k, at column rank - 1 with the same key. On an f32 handle this holds whatever batches the two calls were made
+ * with (every key is the k-ordered fmaf chain). On an fp16 handle it holds when both calls get the same query matrix
+ * (the same nq, hence the same passes and the same GEMM instance; the two fp16 GEMM instances need not round alike).
+ * ms (nullable) = HIP-event times summed over the passes: {query upload + GEMM, the count kernel}.
+ * Argument errors are reported before any device work: MSR_E_INVAL for a null dx / t_ptr, a null q with nq > 0, a null
+ * t_row / output with entries to write, nq < 0, a t_ptr that does not start at 0 or decreases, the precision mismatch;
+ * MSR_E_RANGE for a row or a self_row entry >= n and for more than MSR_DENSE_RANK_MAX_TARGETS targets in one query.
+ * nq == 0 or no target at all returns MSR_OK without a launch and with ms = {0, 0}. The scratch stays with the handle
+ * like the search's (msr_dense_stats). */
+#define MSR_DENSE_RANK_MAX_TARGETS 64 /* listed rows per query */
+int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, const int64_t* t_ptr, const uint32_t* t_row,
+                        const int32_t* self_row, uint32_t* out_rank, uint32_t* out_key, float ms[2]);
 void msr_dense_close(msr_dense* dx);
 /* Bookkeeping of a dense handle: out = {hipMalloc calls made for its scratch so far, scratch bytes it holds, rows, dim}.
  * The scratch of msr_dense_search / msr_hybrid_search stays with the handle and is only ever grown, so repeated calls of

@@ -18,6 +18,7 @@ MSR_KMAX = 1024
 MSR_UNION_MAX = 2 * MSR_KMAX
 MSR_RANK_MAX_TARGETS = 64
 MSR_EXPLAIN_MAX_TARGETS = 64
+MSR_DENSE_RANK_MAX_TARGETS = 64
 MSR_COMM_ID_BYTES = 128
 
 _ERR_NAMES = {
@@ -95,6 +96,7 @@ SYMBOLS = [
     ("msr_dense_search", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("msr_dense_open_f32", _I, [_VP, _U64, _U32, _I, C.POINTER(_VP)]),
     ("msr_dense_search_f32", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("msr_dense_rank_rows", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_dense_close", None, [_VP]),
     ("msr_dense_stats", _I, [_VP, _VP]),
     ("msr_f32_to_f16", _I, [_VP, _VP, _U64, _I]),

@@ -8,6 +8,7 @@
            [--explain N: per-token query weight x doc weight of the first N hits and the judged docs, sparse.explain.tsv]
     python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
+           [--ranks: exact rank of every judged row at any depth (msr_dense_rank_rows) -> the same metrics, dense.ranks.tsv]
 
     python -m mllm_sparse_retrieval_amd eval   --runs_dir runs/ --qrels out/qrels.csv --dataset_name flickr \
            --query_type text [--compat-denominator --world_size 4]                                (recall of TREC runs)
@@ -125,9 +126,10 @@ def _check_search_args(a):
     if a.sparse_index is None and not 1 <= a.depth <= MSR_KMAX:
         sys.exit(f"search: dense-only --depth must be in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth})")
     if getattr(a, "ranks", False):
-        if a.passage_reps is not None:
-            sys.exit("search: --ranks is the sparse-only route (exact ranks come from the sparse index alone): drop "
-                     "--passage_reps")
+        if a.passage_reps is not None and a.sparse_index is not None:
+            sys.exit("search: --ranks ranks on one route, sparse (--sparse_index alone) or dense (--passage_reps alone): a "
+                     "fused score depends on the depth lists, so a rank beyond the depth is not defined; drop "
+                     "--passage_reps or --sparse_index")
         if not a.qrels:
             sys.exit("search: --ranks ranks every query's judged docs and needs --qrels")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -234,9 +236,12 @@ def _cmd_search(a):
     args = SimpleNamespace(depth=a.depth, threads=a.threads, query_type=a.query_type)
     sparse_run, dense_run, fusion_run = {}, {}, {}
     args.batch_size, args.quiet = a.batch_size, True
+    ds = dense_ranks = None
+    if dense_only and getattr(a, "ranks", False):  # the judged rows go through the same open index as the search
+        ds = CrossModalQrels(a.qrels, a.dataset_name)
     t0 = time.time()
     if dense_only:
-        dense_run = _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids)
+        dense_run, dense_ranks = _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids, ds)
     elif p_reps is not None and not a.host_fusion:
         # Hybrid on the GPU (the default): this rank's WHOLE query shard in one msr_hybrid_search call — sparse scores,
         # both depth lists, the reference's fusion (src/hybrid.py:32-53) and the top --fusion_k never leave HBM.
@@ -294,15 +299,16 @@ def _cmd_search(a):
                                 done |= mine
                         for p in parts:
                             os.remove(p)
-    ds = None
     if a.qrels:
-        ds = CrossModalQrels(a.qrels, a.dataset_name)
+        ds = ds or CrossModalQrels(a.qrels, a.dataset_name)
         m = RecallMetrics(ds, dense_run, sparse_run, fusion_run, p_lookup or [], qids, args,
                           denominator=None if (a.compat_denominator or world == 1) else n_queries)
         m.sort_and_count()
         m.all_gather_object()
         m.print_recall()
-    if getattr(a, "ranks", False):
+    if dense_ranks is not None:
+        _report_dense_ranks(a, dense_ranks)
+    elif getattr(a, "ranks", False):
         _report_exact_ranks(a, searcher, ds, qids, texts)
     if getattr(a, "explain", None) is not None:
         _report_explain(a, searcher, ds, qids, texts, sparse_run)
@@ -380,24 +386,81 @@ def _report_explain(a, searcher, ds, qids, texts, sparse_run):
         write_tsv(os.path.join(a.save_dir, "sparse.explain.tsv"), records)
 
 
-def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids):
+def _dense_rank_targets(a, ds, p_lookup, qids):
+    """The judged rows of every query for search --ranks on the dense route: ds.get_target ids mapped to dense rows through
+    p_lookup (first occurrence wins). -> (per query [(docid, row or None)], t_ptr, t_row, self_row or None); a judged id
+    without a row stays in the listing (reported as missing) and is not ranked."""
+    import numpy as np
+
+    from ._cabi import MSR_DENSE_RANK_MAX_TARGETS
+
+    row_of = {}
+    for r, x in enumerate(p_lookup):
+        row_of.setdefault(str(x), r)
+    listing, t_ptr, t_row = [], [0], []
+    for qid in qids:
+        t = ds.get_target(qid, a.query_type)
+        docs = [str(x) for x in t] if isinstance(t, list) else [str(t)]
+        listing.append([(d, row_of.get(d)) for d in docs])
+        t_row.extend(r for _, r in listing[-1] if r is not None)
+        if len(t_row) - t_ptr[-1] > MSR_DENSE_RANK_MAX_TARGETS:
+            sys.exit(f"search: --ranks: query {qid} has {len(t_row) - t_ptr[-1]} judged rows, at most "
+                     f"MSR_DENSE_RANK_MAX_TARGETS = {MSR_DENSE_RANK_MAX_TARGETS}")
+        t_ptr.append(len(t_row))
+    self_row = np.asarray([row_of.get(x, -1) for x in qids], dtype=np.int32) if a.remove_query else None
+    return listing, np.asarray(t_ptr, np.int64), np.asarray(t_row, np.uint32), self_row
+
+
+def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids, ds=None):
     """search --passage_reps without --sparse_index (scripts/search_dense.sh): this rank's WHOLE query shard in one
     DenseIndex.search call. Precision follows the reference (src/search.py:254-270): the f32 flat index it searches on
     the CPU by default, fp16 storage with --use_gpu. Returns the dense run in the layout of get_run_dict
-    (src/search.py:66-82), --remove_query applied there as the reference does."""
+    (src/search.py:66-82), --remove_query applied there as the reference does, and, with `ds` (search --ranks), the exact
+    ranks of every query's judged rows from ONE rank_rows call on the same index and the same normalised query matrix
+    (no depth limit; --remove_query names the row whose id equals the query id as self_row), else None."""
     import numpy as np
 
-    from .dense import DenseIndex
+    from .dense import DenseIndex, keys_to_f32
     from .run import get_run_dict
 
     q = normalize_rows(np.stack([q_reps_by_id[x] for x in qids])) if qids else np.zeros((0, p_reps.shape[1]), np.float32)
+    targets = _dense_rank_targets(a, ds, p_lookup, qids) if ds is not None else None
+    ranked = None
     dix = DenseIndex(p_reps, device=a.device, precision="fp16" if a.use_gpu else "f32")
     try:
         d_scores, d_idx = dix.search(q, min(a.depth, dix.n))
+        if targets is not None:
+            listing, t_ptr, t_row, self_row = targets
+            ranks, keys = dix.rank_rows(q, t_ptr, t_row, self_row)
+            ranked = dict(qids=qids, listing=listing, t_ptr=t_ptr, ranks=ranks, scores=keys_to_f32(keys), n_rows=dix.n)
     finally:
         dix.close()
     lookup = np.asarray([str(x) for x in p_lookup], dtype=object)
-    return get_run_dict(qids, d_scores, lookup[d_idx], a.remove_query)
+    return get_run_dict(qids, d_scores, lookup[d_idx], a.remove_query), ranked
+
+
+def _report_dense_ranks(a, r):
+    """search --ranks on the dense route: prints one line (the figures of ranks.rank_metrics over the exact ranks) and,
+    with --save_dir, writes dense.ranks.tsv: qid, docid, rank, f32 score (repr of the float: reads back bit-exact) per
+    (query, judged id); rank 0 = the query's own row, rank -1 (score 0) = no dense row carries that id."""
+    from .ranks import rank_metrics
+
+    m = rank_metrics(r["ranks"], r["t_ptr"], r["n_rows"])
+    missing = sum(1 for rows in r["listing"] for _, row in rows if row is None)
+    rc = m["recall"]
+    print("Dense exact ranks: r@1 {}, r@5 {}, r@10 {}, r@100 {}, r@200 {}, mrr {}, medr {}, meanr {}, unranked {}, "
+          "missing {}".format(rc[1], rc[5], rc[10], rc[100], rc[200], m["mrr"], m["medr"], m["meanr"], m["n_unranked"],
+                              missing))
+    if a.save_dir:
+        with open(os.path.join(a.save_dir, "dense.ranks.tsv"), "w") as f:
+            e = 0
+            for qid, rows in zip(r["qids"], r["listing"]):
+                for d, row in rows:
+                    if row is None:
+                        f.write(f"{qid}\t{d}\t-1\t0\n")
+                    else:
+                        f.write(f"{qid}\t{d}\t{int(r['ranks'][e])}\t{float(r['scores'][e])!r}\n")
+                        e += 1
 
 
 def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
@@ -553,9 +616,11 @@ def main(argv=None):
     s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs (with or without --fusion_union; "
                                                                    "the fused run then feeds the recall report only: fusion.trec is written beside a dense run)")
     s.add_argument("--ranks", action="store_true",
-                   help="sparse search: after the search, the EXACT rank (no depth limit) of every query's --qrels docs "
-                        "from one msr_rank_docs call; prints recall, MRR, MedR, MeanR and writes sparse.ranks.tsv under "
-                        "--save_dir; honours --remove_query; not with --passage_reps or under a launcher")
+                   help="sparse search (--sparse_index alone) or dense search (--passage_reps alone, f32 or --use_gpu): after "
+                        "the search, the EXACT rank (no depth limit) of every query's --qrels docs from one msr_rank_docs / "
+                        "msr_dense_rank_rows call; prints recall, MRR, MedR, MeanR and writes sparse.ranks.tsv / "
+                        "dense.ranks.tsv under --save_dir; honours --remove_query; not on the hybrid route (--passage_reps "
+                        "with --sparse_index) or under a launcher")
     s.add_argument("--explain", type=int, default=None, metavar="N",
                    help="sparse search: after the search, WHY the first N hits of every query (1 <= N <= 64; after "
                         "--remove_query's filter) and, with --qrels, its judged docs score what they score: per-token "

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "msr_accumulate.hpp"
+#include "msr_dense_rank.hpp"
 #include "msr_gemm_f32.hpp"
 #include "msr_gemm_w4.hpp"
 
@@ -132,7 +133,7 @@ struct msr_dense {
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
     // grown: six hipMalloc / hipFree pairs of up to 200 MB cost a call more than its kernels
     enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_USRC, S_USPARSE, S_UDENSE,
-                S_URANGE, S_COUNT };
+                S_URANGE, S_RANK_IN, S_RANK_OUT, S_COUNT };
     void* scratch[S_COUNT] = {};
     size_t scratch_bytes[S_COUNT] = {};
     uint64_t n_device_allocs = 0;  // hipMalloc calls made on behalf of this handle (steady-state calls make none)
@@ -304,6 +305,54 @@ static int launch_dense_gemm_f32(msr_dense* dx, const float* P, const float* d_Q
     return MSR_OK;
 }
 
+// The passes of one dense call over `nq` queries, shared by the search and by msr_dense_rank_rows (so both walk the same
+// passes with the same GEMM instances): queries per pass, the device query copy's row size and the doc columns scored.
+struct DensePasses {
+    uint32_t qt_pad;   // rows of d_Q / d_S per pass (a multiple of 256)
+    uint32_t qt;       // queries per pass
+    size_t q_row;      // bytes per row of the device query copy
+    uint64_t n_cover;  // the GEMM writes doc columns [0, n_cover) of every score row; [n_cover, n_pad) are never written
+};
+
+static DensePasses dense_passes(const msr_dense* dx, int nq) {
+    DensePasses ps;
+    // queries per pass: score rows of at most ~256 MB (they are read back by select_tiles out of the Infinity Cache, and
+    // the buffer stays with the handle), the GEMM grid filling its last round of 256 CUs as well as it can
+    const uint32_t nq_pad_all = (uint32_t)((std::max(nq, 1) + 255) / 256 * 256);
+    const uint64_t rb_max = std::max<uint64_t>(1, (256ull << 20) / (std::max<uint64_t>(dx->n_pad, 256) * 4 * 256));
+    ps.qt_pad = 256u * pick_row_blocks((uint32_t)(std::max<uint64_t>(dx->n_pad, 256) / 256), rb_max, nq_pad_all / 256);
+    ps.qt = (uint32_t)std::min<uint32_t>(ps.qt_pad, std::max(nq, 1));
+    ps.q_row = dx->f32 ? (size_t)dx->hp * 4 : (size_t)dx->h * 2;
+    // doc blocks: up to the end of the last select round that holds a real doc (a round = 4 docs x threads of
+    // the select instance: 1024 docs at 4096-doc tiles, 2048 at 8192); padding beyond that is never read
+    const uint64_t round_docs = dx->tile_docs == 4096 ? 1024 : 2048;
+    ps.n_cover = std::min<uint64_t>(dx->n_pad, (dx->n + round_docs - 1) / round_docs * round_docs);
+    return ps;
+}
+
+// One pass: queries [q0, q0 + qn) of q_host into d_Q (rows zero padded to a multiple of 256, K to the handle's row size)
+// and their keys into d_S[q][n_pad], all on dx->stream. e0 is recorded before the upload (time_upload) or after it.
+static int dense_pass_scores(msr_dense* dx, const DensePasses& ps, const void* q_host, int q0, uint32_t qn, uint8_t* d_Q,
+                             uint32_t* d_S, hipEvent_t e0, bool time_upload, const char* who) {
+    const uint32_t qn_pad = (qn + 255) / 256 * 256;
+    // f32 rows land in a K-padded copy (zero columns are neutral in the fmaf chain), fp16 rows as they are
+    const size_t h_row = (size_t)dx->h * (dx->f32 ? 4 : 2);
+    const bool c = (!time_upload || hipEventRecord(e0, dx->stream) == hipSuccess) &&
+                   hipMemsetAsync(d_Q, 0, (size_t)qn_pad * ps.q_row, dx->stream) == hipSuccess &&
+                   (ps.q_row == h_row
+                        ? hipMemcpyAsync(d_Q, (const uint8_t*)q_host + (size_t)q0 * h_row, (size_t)qn * h_row,
+                                         hipMemcpyHostToDevice, dx->stream)
+                        : hipMemcpy2DAsync(d_Q, ps.q_row, (const uint8_t*)q_host + (size_t)q0 * h_row, h_row, h_row, qn,
+                                           hipMemcpyHostToDevice, dx->stream)) == hipSuccess &&
+                   (time_upload || hipEventRecord(e0, dx->stream) == hipSuccess);
+    if (!c) {
+        set_error("query upload failed in %s", who);
+        return MSR_E_HIP;
+    }
+    return dx->f32 ? launch_dense_gemm_f32(dx, dx->d_P32, (const float*)d_Q, d_S, qn, qn_pad, ps.n_cover, dx->n_pad, dx->stream)
+                   : launch_dense_gemm(dx, dx->d_P, (const _Float16*)d_Q, d_S, qn, qn_pad, ps.n_cover, dx->n_pad, dx->stream);
+}
+
 // to_device = true: out_* are DEVICE buffers ([nq][k] / [nq]) filled on dx->stream (hybrid path); else host buffers.
 // q: [nq][h] fp16 (uint16_t) or, on an f32 handle, f32 rows.
 static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
@@ -317,19 +366,14 @@ static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, u
         return MSR_E_RANGE;
     }
     HIP_TRY(hipSetDevice(dx->device));
-    // queries per pass: score rows of at most ~256 MB (they are read back by select_tiles out of the Infinity Cache, and
-    // the buffer stays with the handle), the GEMM grid filling its last round of 256 CUs as well as it can
-    const uint32_t nq_pad_all = (uint32_t)((std::max(nq, 1) + 255) / 256 * 256);
-    const uint64_t rb_max = std::max<uint64_t>(1, (256ull << 20) / (std::max<uint64_t>(dx->n_pad, 256) * 4 * 256));
-    const uint32_t qt_pad = 256u * pick_row_blocks((uint32_t)(std::max<uint64_t>(dx->n_pad, 256) / 256), rb_max, nq_pad_all / 256);
-    const uint32_t qt = (uint32_t)std::min<uint32_t>(qt_pad, std::max(nq, 1));
+    const DensePasses ps = dense_passes(dx, nq);
+    const uint32_t qt = ps.qt;
     int rc = MSR_OK;
     const size_t perq = std::max<size_t>((size_t)qt * k, 1);
-    const size_t q_row = dx->f32 ? (size_t)dx->hp * 4 : (size_t)dx->h * 2;  // bytes per row of the device query copy
     // device scratch and events live on the handle (only ever grown): at the reference's --batch_size 2
     // (scripts/search.sh:29) seven hipMalloc / hipFree pairs per call cost more than the search
-    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)qt_pad * q_row);
-    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)qt_pad * dx->n_pad * 4);
+    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
+    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
     uint64_t* d_part = (uint64_t*)dx->take(msr_dense::S_PART, (size_t)dx->n_tiles * perq * 8);
     uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perq * 4);
     uint32_t* d_su = (uint32_t*)dx->take(msr_dense::S_SU, perq * 4);
@@ -346,27 +390,7 @@ static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, u
     double t_gemm = 0, t_sel = 0;
     for (int q0 = 0; q0 < nq && rc == MSR_OK; q0 += (int)qt) {
         const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
-        const uint32_t qn_pad = (qn + 255) / 256 * 256;
-        // f32 rows land in a K-padded copy (zero columns are neutral in the fmaf chain), fp16 rows as they are
-        const size_t h_row = (size_t)dx->h * (dx->f32 ? 4 : 2);
-        bool c = hipMemsetAsync(d_Q, 0, (size_t)qn_pad * q_row, dx->stream) == hipSuccess &&
-                 (q_row == h_row
-                      ? hipMemcpyAsync(d_Q, (const uint8_t*)q_host + (size_t)q0 * h_row, (size_t)qn * h_row,
-                                       hipMemcpyHostToDevice, dx->stream)
-                      : hipMemcpy2DAsync(d_Q, q_row, (const uint8_t*)q_host + (size_t)q0 * h_row, h_row, h_row, qn,
-                                         hipMemcpyHostToDevice, dx->stream)) == hipSuccess &&
-                 hipEventRecord(e0, dx->stream) == hipSuccess;
-        if (!c) {
-            set_error("query upload failed in msr_dense_search");
-            rc = MSR_E_HIP;
-            break;
-        }
-        // doc blocks: up to the end of the last select round that holds a real doc (a round = 4 docs x threads of
-        // the select instance: 1024 docs at 4096-doc tiles, 2048 at 8192); padding beyond that is never read
-        const uint64_t round_docs = dx->tile_docs == 4096 ? 1024 : 2048;
-        const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, (dx->n + round_docs - 1) / round_docs * round_docs);
-        rc = dx->f32 ? launch_dense_gemm_f32(dx, dx->d_P32, (const float*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream)
-                     : launch_dense_gemm(dx, dx->d_P, (const _Float16*)d_Q, d_S, qn, qn_pad, n_cover, dx->n_pad, dx->stream);
+        rc = dense_pass_scores(dx, ps, q_host, q0, qn, d_Q, d_S, e0, false, "msr_dense_search");
         if (rc != MSR_OK) break;
         (void)hipEventRecord(e1, dx->stream);
         SelectArgs se;
@@ -399,10 +423,10 @@ static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, u
         if (rc != MSR_OK) break;
         (void)hipEventRecord(e2, dx->stream);
         const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_ord, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
-            hipMemcpyAsync(out_key + (size_t)q0 * k, d_su, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
-            hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, kind, dx->stream) == hipSuccess &&
-            hipStreamSynchronize(dx->stream) == hipSuccess;
+        const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_ord, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_key + (size_t)q0 * k, d_su, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, kind, dx->stream) == hipSuccess &&
+                       hipStreamSynchronize(dx->stream) == hipSuccess;
         if (!c) {
             set_error("dense search kernels or result download failed: %s", hipGetErrorString(hipGetLastError()));
             rc = MSR_E_HIP;
@@ -449,6 +473,129 @@ int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t*
         return MSR_E_INVAL;
     }
     return dense_search_impl(dx, q, nq, k, out_idx, out_key, out_n, gemm_ms, select_ms, false);
+}
+
+// Exact ranks of listed rows: the passes and the GEMM of the search (dense_passes / dense_pass_scores), then ONE count
+// kernel per pass over the score rows (msr_dense_rank.hpp) in the place of select + merge. Per pass one upload
+// {t_ptr rebased to the pass | self | the pass's slice of t_row} and the ranks and keys of its entries back.
+int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, const int64_t* t_ptr, const uint32_t* t_row,
+                        const int32_t* self_row, uint32_t* out_rank, uint32_t* out_key, float ms[2]) {
+    const char* const who = "msr_dense_rank_rows";
+    // ---- checks, all before any device work
+    if (!dx || !t_ptr || nq < 0 || (nq && !q)) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if (t_ptr[0] != 0) {
+        set_error("%s: t_ptr must start at 0 (got %lld)", who, (long long)t_ptr[0]);
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i)
+        if (t_ptr[i + 1] < t_ptr[i]) {
+            set_error("%s: t_ptr decreases at query %d", who, i);
+            return MSR_E_INVAL;
+        }
+    const int64_t n_ent = t_ptr[nq];
+    if (n_ent && (!t_row || !out_rank || !out_key)) {
+        set_error("%s: null t_row / out_rank / out_key with %lld listed rows", who, (long long)n_ent);
+        return MSR_E_INVAL;
+    }
+    if ((q_is_f32 != 0) != dx->f32) {
+        if (dx->f32)
+            set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
+                      "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
+        else
+            set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
+                      "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < nq; ++i) {
+        if (t_ptr[i + 1] - t_ptr[i] > MSR_DENSE_RANK_MAX_TARGETS) {
+            set_error("%s: query %d lists %lld rows, at most MSR_DENSE_RANK_MAX_TARGETS = %d", who, i,
+                      (long long)(t_ptr[i + 1] - t_ptr[i]), MSR_DENSE_RANK_MAX_TARGETS);
+            return MSR_E_RANGE;
+        }
+        if (self_row && self_row[i] >= 0 && (uint64_t)self_row[i] >= dx->n) {
+            set_error("%s: self_row[%d] = %d, the index holds %llu rows", who, i, self_row[i], (unsigned long long)dx->n);
+            return MSR_E_RANGE;
+        }
+    }
+    for (int64_t e = 0; e < n_ent; ++e)
+        if (t_row[e] >= dx->n) {
+            set_error("%s: listed row %u at entry %lld, the index holds %llu rows", who, t_row[e], (long long)e,
+                      (unsigned long long)dx->n);
+            return MSR_E_RANGE;
+        }
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (nq == 0 || n_ent == 0) return MSR_OK;
+    // ---- scratch of the largest pass
+    HIP_TRY(hipSetDevice(dx->device));
+    const DensePasses ps = dense_passes(dx, nq);
+    const int qt = (int)ps.qt;
+    int64_t max_pe = 0;
+    for (int q0 = 0; q0 < nq; q0 += qt) max_pe = std::max<int64_t>(max_pe, t_ptr[std::min(nq, q0 + qt)] - t_ptr[q0]);
+    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
+    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
+    uint32_t* d_in = (uint32_t*)dx->take(msr_dense::S_RANK_IN, ((size_t)2 * qt + 1 + (size_t)max_pe) * 4);
+    uint32_t* d_out = (uint32_t*)dx->take(msr_dense::S_RANK_OUT, (size_t)2 * max_pe * 4);
+    bool ok = d_Q && d_S && d_in && d_out;
+    for (hipEvent_t& e : dx->ev)
+        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
+    if (!ok) {
+        set_error("device allocation failed in %s (%d queries per pass x %llu docs)", who, qt, (unsigned long long)dx->n_pad);
+        return MSR_E_NOMEM;
+    }
+    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
+    std::vector<uint32_t> in;  // host image of the pass's upload
+    double t_gemm = 0, t_count = 0;
+    for (int q0 = 0; q0 < nq; q0 += qt) {
+        const uint32_t qn = (uint32_t)std::min(qt, nq - q0);
+        const int64_t ent0 = t_ptr[q0];
+        const uint32_t pe = (uint32_t)(t_ptr[q0 + qn] - ent0);
+        if (pe == 0) continue;  // nothing listed in this pass: no GEMM either
+        in.assign((size_t)2 * qn + 1 + pe, 0u);
+        uint32_t t_max = 0;
+        for (uint32_t i = 0; i <= qn; ++i) in[i] = (uint32_t)(t_ptr[q0 + i] - ent0);
+        for (uint32_t i = 0; i < qn; ++i) {
+            in[qn + 1 + i] = (uint32_t)(self_row ? std::max<int32_t>(self_row[q0 + i], -1) : -1);
+            t_max = std::max(t_max, in[i + 1] - in[i]);
+        }
+        std::copy(t_row + ent0, t_row + ent0 + pe, in.begin() + 2 * qn + 1);
+        if (hipMemcpyAsync(d_in, in.data(), in.size() * 4, hipMemcpyHostToDevice, dx->stream) != hipSuccess) {
+            set_error("%s: upload of the listed rows failed", who);
+            return MSR_E_HIP;
+        }
+        const int rc = dense_pass_scores(dx, ps, q, q0, qn, d_Q, d_S, e0, true, who);
+        if (rc != MSR_OK) return rc;
+        (void)hipEventRecord(e1, dx->stream);
+        DenseRankArgs ra;
+        ra.S = d_S;
+        ra.ld = dx->n_pad;
+        ra.n = (uint32_t)dx->n;
+        ra.t_ptr = d_in;
+        ra.self_row = reinterpret_cast<const int32_t*>(d_in + qn + 1);
+        ra.t_row = d_in + 2 * qn + 1;
+        ra.out_rank = d_out;
+        ra.out_key = d_out + pe;
+        hipLaunchKernelGGL(dense_rank_rows, dim3(qn, (t_max + kDenseRankGroup - 1) / kDenseRankGroup), dim3(kDenseRankThreads), 0,
+                           dx->stream, ra);
+        HIP_TRY(hipGetLastError());
+        (void)hipEventRecord(e2, dx->stream);
+        const bool c = hipMemcpyAsync(out_rank + ent0, d_out, (size_t)pe * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_key + ent0, d_out + pe, (size_t)pe * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipStreamSynchronize(dx->stream) == hipSuccess;
+        if (!c) {
+            set_error("%s: kernels or result download failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return MSR_E_HIP;
+        }
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, e0, e1);
+        (void)hipEventElapsedTime(&b, e1, e2);
+        t_gemm += a;
+        t_count += b;
+    }
+    if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_count;
+    return MSR_OK;
 }
 
 }  // extern "C"

@@ -92,6 +92,7 @@ class DenseIndex:
             self.n = p16.shape[0]
             check(lib().msr_dense_open(ptr(p16.view(np.uint16)), self.n, p16.shape[1], int(device), C.byref(self._h)))
         self.last_ms = (0.0, 0.0)
+        self.last_rank_ms = (0.0, 0.0)
 
     def search_keys(self, q_reps, k):
         """-> (row indices uint32 [nq,k], order-preserving u32 score keys [nq,k], hit counts int32 [nq]) as the C-ABI
@@ -118,6 +119,34 @@ class DenseIndex:
         scores = np.where(valid, keys_to_f32(key), -np.inf).astype(np.float32)
         indices = np.where(valid, idx.astype(np.int64), -1)
         return scores, indices
+
+    def rank_rows(self, q_reps, t_ptr, t_row, self_row=None):
+        """Exact rank (1 = best; no depth limit) and score key of listed rows (msr_dense_rank_rows, include/msr.h): query i
+        owns t_row[t_ptr[i]:t_ptr[i + 1]] (dense row indices, at most MSR_DENSE_RANK_MAX_TARGETS each, duplicates
+        allowed); self_row[i] >= 0 names the row that does not count for query i (remove_query), whose own rank is 0.
+        -> (ranks uint32, keys uint32), indexed like t_row; keys_to_f32(keys) are the scores."""
+        if self.precision == "f32":
+            q = _as_f32_rows(q_reps, self.dim)
+            q_ptr, is_f32 = ptr(q), 1
+        else:
+            q = _as_fp16_rows(q_reps, self.dim, self)   # (consumed by the synchronous call below)
+            q_ptr, is_f32 = ptr(q.view(np.uint16)), 0
+        nq = q.shape[0]
+        t_ptr = np.ascontiguousarray(t_ptr, dtype=np.int64)
+        t_row = np.ascontiguousarray(t_row, dtype=np.uint32)
+        if t_ptr.shape != (nq + 1,) or t_row.ndim != 1 or t_ptr[-1] != len(t_row):
+            raise ValueError(f"malformed CSR target arrays: t_ptr needs {nq + 1} entries ending at len(t_row) = "
+                             f"{t_row.size}, got shape {t_ptr.shape}")
+        so = None if self_row is None else np.ascontiguousarray(self_row, dtype=np.int32)
+        if so is not None and so.shape != (nq,):
+            raise ValueError(f"self_row needs one entry per query ({nq}), got shape {so.shape}")
+        ranks = np.zeros(len(t_row), dtype=np.uint32)
+        keys = np.zeros(len(t_row), dtype=np.uint32)
+        ms = (C.c_float * 2)()
+        check(lib().msr_dense_rank_rows(self._h, q_ptr, is_f32, nq, ptr(t_ptr), ptr(t_row), ptr(so), ptr(ranks), ptr(keys),
+                                        ms))
+        self.last_rank_ms = (ms[0], ms[1])
+        return ranks, keys
 
     def stats(self):
         """{'device_allocs': hipMalloc calls made for this handle's scratch, 'scratch_bytes': what it holds}."""

@@ -216,8 +216,9 @@ int msr_batch_kernel_ms(msr_batch* b, float* score_ms, float* merge_ms);
  * index's stream), so a whole timed region can be priced without a host sync per call. */
 int msr_batch_timing_reset(msr_batch* b);
 int msr_batch_timing_sum(msr_batch* b, int* n_calls, float* score_ms, float* merge_ms);
-/* Kept for ABI compatibility: the kernels' phase stamps were retired, so this writes eight zeros and returns MSR_OK
- * (MSR_E_INVAL for a null batch or output). */
+/* Kept for ABI compatibility: the kernels' phase stamps were retired, so out[0..6] are zeros. out[7] = the searches of
+ * this batch that took the one-workgroup-per-query walk of small indexes instead of the staged launches.
+ * Returns MSR_OK (MSR_E_INVAL for a null batch or output). */
 int msr_batch_debug_stamps(msr_batch* b, unsigned long long out[8]);
 /* Algorithmic bytes of one search of this batch, SURVEY.md §8d:
  * sum over queries of  sum_t df(t)*(4+2) + |q|*12 + k*8  (df restricted to this handle's shard). */

@@ -258,10 +258,43 @@ __device__ __forceinline__ void accumulate_tile(const ScoreArgs& a, const uint32
 // a ballot + four v_readlane each, and has its first UL chunk loads IN FLIGHT before the accumulators are initialised,
 // so the posting latency hides behind the dense-head / zeroing phase. Two barriers in all (accumulators initialised;
 // accumulation complete).
-template <int TILE_DOCS, int NT>
-__device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const uint32_t q, const uint32_t tile_l,
-                                                      const int rounds, uint8_t* const lds, SelectScratch& ss,
-                                                      const uint32_t tid) {
+
+// The query side of the light accumulation, per wave in registers: the same for every tile the query is scored against.
+struct LightQuery {
+    uint32_t cnt;       // sparse terms (<= 64: the host picks this path only when every query fits)
+    uint32_t pmask;     // bit mask of the dense-head pairs the query holds
+    uint32_t s_t, s_w;  // lane j < cnt: the query's j-th sparse term and its weight
+    uint32_t qv;        // lane p < n_pairs: packed query weights of dense-head pair p
+};
+__device__ __forceinline__ LightQuery load_light_query(const ScoreArgs& a, const uint32_t q, const uint32_t lane) {
+    LightQuery lq;
+    const uint4 meta = a.q_meta[q];  // {first term, end term, dense-head pair mask}
+    lq.cnt = min(meta.y - meta.x, 64u);
+    lq.pmask = meta.z;
+    lq.s_t = lq.s_w = 0;
+    if (lane < lq.cnt) {
+        lq.s_t = a.q_term[meta.x + lane];
+        lq.s_w = a.q_w[meta.x + lane];
+    }
+    lq.qv = lane < a.n_pairs ? a.q_dense[(uint64_t)q * a.n_pairs + lane] : 0u;
+    return lq;
+}
+// The tile side: where the tile's segment row, postings and dense-head rows live (score_tiles computes it per
+// workgroup; score_tiles_walk reads it from the handle's per-tile table, msr_walk.hpp).
+struct LightTile {
+    global_u32 seg_row;       // the tile's row of seg_ptr (typed as device memory: the walk reads it out of a table)
+    uint32_t tile_first;      // seg_row[0]: first vec of the tile
+    const char* post_base;    // address of that vec
+    const char* dense;        // the tile's dense-head rows [n_pairs][TILE_DOCS]
+    uint32_t dense_bytes;
+    int rounds;               // rounds of 4*NT accumulators that hold real docs
+};
+
+// `init_barrier()` runs between the accumulator init and the first LDS atomic and must hold the workgroup barrier
+// (score_tiles resets the selection scratch before it, score_tiles_walk seeds the candidate buffer after it).
+template <int TILE_DOCS, int NT, class InitBarrier>
+__device__ __forceinline__ void accumulate_light(const LightQuery& lq, const LightTile& lt, uint8_t* const lds,
+                                                 const uint32_t tid, InitBarrier&& init_barrier) {
     constexpr int NW = NT / 64;
     constexpr int UL = 4;  // chunk loads per wave and batch
     static_assert(TILE_DOCS % (4 * NT) == 0, "tile must be a multiple of 4*NT");
@@ -271,17 +304,12 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
     const uint32_t wave = rfl(tid >> 6);
     uint4* const a4 = reinterpret_cast<uint4*>(acc);
 
-    const uint4 meta = a.q_meta[q];  // {first term, end term, dense-head pair mask}
-    const uint32_t qb = meta.x, cnt = min(meta.y - meta.x, 64u);  // (the host picks this path only when every query fits)
-    const uint32_t* seg_row = a.seg_ptr + (uint64_t)tile_l * (a.n_terms + 1);
-    const uint32_t tile_first = seg_row[0];
-    const char* const post_base = reinterpret_cast<const char*>(a.postings) + (uint64_t)(tile_first - a.vec_base) * 16u;
-    const bool has = lane < cnt;
-    uint32_t s_t = 0, s_w = 0;
-    if (has) {
-        s_t = a.q_term[qb + lane];
-        s_w = a.q_w[qb + lane];
-    }
+    const global_u32 seg_row = lt.seg_row;
+    const uint32_t tile_first = lt.tile_first;
+    const char* const post_base = lt.post_base;
+    const int rounds = lt.rounds;
+    const bool has = lane < lq.cnt;
+    const uint32_t s_t = lq.s_t, s_w = lq.s_w;
     // chunk data of this wave's first UL chunks: requested inside the init phase, consumed after it
     uint4 v[UL];
     uint32_t n16[UL], wq[UL];
@@ -289,8 +317,7 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
     auto resolve_and_load = [&](uint32_t u0) {  // chunks u0 .. u0+UL-1 of this wave (chunk index c = wave + u * NW)
 #pragma unroll
         for (int u = 0; u < UL; ++u) {
-            n16[u] = 0;
-            v[u] = make_uint4(0, 0, 0, 0);
+            n16[u] = 0;  // (an idle slot: v[u] and wq[u] are not read)
             if (u0 + (uint32_t)u < count_w) {  // wave-uniform: most waves of a light query hold one or two chunks
                 const uint32_t c = wave + (u0 + (uint32_t)u) * NW;
                 // pref is non-decreasing over the lanes: the lanes with pref <= c are a prefix, its last lane owns chunk c
@@ -313,9 +340,12 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
                 for (int e = 0; e < 4; ++e) atomicAdd(&acc[p[e] & 0xFFFFu], __umul24(p[e] >> 16, wq[u]));
             }
     };
-    auto prefetch = [&]() {  // segment table, chunk scan, first chunk loads: all per wave, in registers
+    auto lookup_and_scan = [&]() {  // segment table and chunk scan: per wave, in registers
         if (has) {
-            const uint32_t s0 = seg_row[s_t], s1 = seg_row[s_t + 1];
+            // (a 32-bit byte offset from the uniform row base — a row is shorter than 4 GiB, checked when the index is
+            // attached — so the lookups need one address register, not two 64-bit pairs)
+            const global_u32 seg = (global_u32)((const __attribute__((address_space(1))) char*)seg_row + (s_t << 2));
+            const uint32_t s0 = seg[0], s1 = seg[1];
             s_start = s0 - tile_first;
             s_len = s1 - s0;
         }
@@ -324,6 +354,9 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
         pref = inc - nch;
         const uint32_t total = rdl(inc, 63);
         count_w = total > wave ? (total - wave + NW - 1) / NW : 0u;
+    };
+    auto prefetch = [&]() {
+        lookup_and_scan();
         resolve_and_load(0);
     };
 
@@ -332,11 +365,9 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
     {
         typedef unsigned short us2 __attribute__((ext_vector_type(2)));
         constexpr int RG = 4;
-        const uint32_t qv = lane < a.n_pairs ? a.q_dense[(uint64_t)q * a.n_pairs + lane] : 0u;
-        const uint32_t pmask = meta.z;
-        const __amdgpu_buffer_rsrc_t rs_dense =
-            make_rsrc(reinterpret_cast<const char*>(a.dense) + (uint64_t)tile_l * a.n_pairs * (TILE_DOCS * 4u),
-                      a.n_pairs * (uint32_t)(TILE_DOCS * 4));
+        const uint32_t qv = lq.qv;
+        const uint32_t pmask = lq.pmask;
+        const __amdgpu_buffer_rsrc_t rs_dense = make_rsrc(lt.dense, lt.dense_bytes);
         for (int r0 = 0; r0 < rounds; r0 += RG) {
             uint4 sacc[RG];
 #pragma unroll
@@ -376,19 +407,42 @@ __device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const 
         }
         if (!pmask) prefetch();
     }
-    if (tid < 64) ss.cnt[tid] = 0;
-    if (tid == 0) {
-        ss.n_cand = 0;
-        ss.tau0 = 1;
-        ss.smax = 0;
-    }
-    __syncthreads();  // every accumulator is initialised
+    init_barrier();  // every accumulator is initialised
     add_loaded();
-    for (uint32_t u0 = UL; u0 < count_w; u0 += UL) {  // (rare on this path: more than UL chunks for one wave)
-        resolve_and_load(u0);
-        add_loaded();
+    if (count_w > UL) {  // rare on this path: more than UL chunks for one wave
+        // (the segment table is looked up again, L2-hot, instead of living in three registers through the init phase,
+        // where the kernels that walk several tiles have none to spare)
+        lookup_and_scan();
+        for (uint32_t u0 = UL; u0 < count_w; u0 += UL) {
+            resolve_and_load(u0);
+            add_loaded();
+        }
     }
     __syncthreads();  // accumulation complete
+}
+
+// One (tile, query) workgroup of score_tiles and of the rank / hybrid kernels: query and tile side computed here.
+template <int TILE_DOCS, int NT>
+__device__ __forceinline__ void accumulate_tile_light(const ScoreArgs& a, const uint32_t q, const uint32_t tile_l,
+                                                      const int rounds, uint8_t* const lds, SelectScratch& ss,
+                                                      const uint32_t tid) {
+    LightTile lt;
+    lt.seg_row = (global_u32)(a.seg_ptr + (uint64_t)tile_l * (a.n_terms + 1));
+    lt.tile_first = lt.seg_row[0];
+    lt.post_base = reinterpret_cast<const char*>(a.postings) + (uint64_t)(lt.tile_first - a.vec_base) * 16u;
+    lt.dense = reinterpret_cast<const char*>(a.dense) + (uint64_t)tile_l * a.n_pairs * (TILE_DOCS * 4u);
+    lt.dense_bytes = a.n_pairs * (uint32_t)(TILE_DOCS * 4);
+    lt.rounds = rounds;
+    const LightQuery lq = load_light_query(a, q, tid & 63);
+    accumulate_light<TILE_DOCS, NT>(lq, lt, lds, tid, [&] {
+        if (tid < 64) ss.cnt[tid] = 0;
+        if (tid == 0) {
+            ss.n_cand = 0;
+            ss.tau0 = 1;
+            ss.smax = 0;
+        }
+        __syncthreads();
+    });
 }
 
 }  // namespace msr

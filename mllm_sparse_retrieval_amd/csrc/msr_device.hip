@@ -11,6 +11,7 @@
 #include <chrono>
 
 #include "msr_kernels.hpp"
+#include "msr_walk.hpp"
 #include "msr_rank.hpp"
 #include "msr_explain.hpp"
 
@@ -42,6 +43,28 @@ static int launch_score(hipStream_t st, uint32_t tile_docs, uint32_t t_begin, ui
         if (!known) return no_tile_shape(tile_docs);
         HIP_TRY(hipGetLastError());
     }
+    return MSR_OK;
+}
+
+// score_tiles_walk over queries [0, a.s.nq): one workgroup per query, the k <= 512 instance's waves. Only the tile shapes
+// with a light scorer have an instance (walk_route's table exists for no other).
+static int launch_walk(hipStream_t st, uint32_t tile_docs, const WalkArgs& a) {
+    if (a.s.nq == 0) return MSR_OK;
+    if (a.n_tiles < 2 || a.n_tiles > kWalkMaxTiles || a.m.k > kWalkMaxK || !a.s.light || !a.tiles) {
+        set_error("score_tiles_walk: %u tiles, k=%u outside its instances", a.n_tiles, a.m.k);
+        return MSR_E_RANGE;
+    }
+    bool known = false;
+    with_tile_shape(tile_docs, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::light) {
+            constexpr uint32_t W = S::docs == 8192 ? 8 : 7;  // waves per SIMD at the LDS cap: 4 x 8 and 7 x 4 waves per CU
+            hipLaunchKernelGGL((score_tiles_walk<S::docs, S::threads, W>), dim3(a.s.nq), dim3(S::threads), 0, st, a);
+            known = true;
+        }
+    });
+    if (!known) return no_tile_shape(tile_docs);
+    HIP_TRY(hipGetLastError());
     return MSR_OK;
 }
 
@@ -123,6 +146,46 @@ static int launch_explain(hipStream_t st, uint32_t tile_docs, uint32_t n_pairs, 
 }
 
 // ------------------------------------------------------------------------------------------------ residency
+// The tile side of score_tiles_walk for the handle's tiles: per tile what score_tiles computes from ScoreArgs
+// (seg_ptr + tile_l * (n_terms + 1); postings + (tile_first - vec_base) * 16; dense + tile_l * n_pairs * tile_docs * 4;
+// doc0 = global tile * tile_docs; rounds = ceil(docs of the tile / (4 * threads))). The three bases are addresses
+// (0: the entries hold byte offsets).
+static void fill_walk_tiles(const msr_index* ix, uint64_t seg_base, uint64_t post_base, uint64_t dense_base,
+                            uint32_t n_pairs, WalkTile* out) {
+    const IndexHeader* h = ix->host.h;
+    const uint64_t stride = (uint64_t)h->n_terms + 1, nt4 = 4ull * tile_threads(h->tile_docs);
+    const uint32_t* sp = ix->host.seg_ptr + (uint64_t)ix->shard_tile0 * stride;
+    for (uint32_t t = 0; t < ix->shard_ntiles; ++t) {
+        const uint64_t doc0 = (uint64_t)(ix->shard_tile0 + t) * h->tile_docs;
+        const uint64_t ndocs = std::min<uint64_t>(h->tile_docs, h->n_docs - doc0);
+        WalkTile& w = out[t];
+        w.tile_first = sp[t * stride];
+        w.seg_row = reinterpret_cast<const uint32_t*>(seg_base + t * stride * 4);
+        w.post_base = reinterpret_cast<const char*>(post_base + (uint64_t)(w.tile_first - sp[0]) * 16);
+        w.dense = reinterpret_cast<const char*>(dense_base + (uint64_t)t * n_pairs * h->tile_docs * 4);
+        w.doc0_rounds = (uint32_t)doc0 | (uint32_t)((ndocs + nt4 - 1) / nt4);
+    }
+}
+
+// Does a handle on this index get a WalkTile table? (Every term resident, a tile shape with a light scorer, 2 ..
+// kWalkMaxTiles tiles, doc ordinals that leave doc0_rounds' low bits free.)
+static bool walk_table_wanted(const msr_index* ix) {
+    const IndexHeader* h = ix->host.h;
+    return ix->term_nshards == 0 && hybrid_tile(h->tile_docs) && ix->shard_ntiles >= 2 && ix->shard_ntiles <= kWalkMaxTiles &&
+           (uint64_t)h->n_tiles * h->tile_docs <= 0xFFFFFFFFull;
+}
+
+// internal, not part of include/msr.h (tests/test_walk.py): the table of a handle as byte offsets from the three bases;
+// out holds shard_ntiles entries of 32 bytes. MSR_E_INVAL: this handle never walks.
+extern "C" int walk_tile_table(const msr_index* ix, void* out) {
+    if (!ix || !out || !walk_table_wanted(ix)) {
+        set_error("walk_tile_table: no table for this handle");
+        return MSR_E_INVAL;
+    }
+    fill_walk_tiles(ix, 0, 0, 0, ix->host.h->n_dense / 2, static_cast<WalkTile*>(out));
+    return MSR_OK;
+}
+
 int device_attach(msr_index* ix, int device) {
     int n_dev = 0;
     hipError_t e = hipGetDeviceCount(&n_dev);
@@ -137,6 +200,10 @@ int device_attach(msr_index* ix, int device) {
     }
     const IndexHeader* h = ix->host.h;
     if (!tile_threads(h->tile_docs)) return no_tile_shape(h->tile_docs);
+    if (h->n_terms >= (1u << 30)) {  // the light scorers look a term's segment up at a 32-bit byte offset into the tile's row
+        set_error("index holds %u terms (>= 2^30)", h->n_terms);
+        return MSR_E_RANGE;
+    }
     DeviceIndex* d = new (std::nothrow) DeviceIndex;
     if (!d) {
         set_error("out of host memory");
@@ -247,6 +314,16 @@ int device_attach(msr_index* ix, int device) {
                 return fail(MSR_E_HIP);
             }
             d->resident_bytes = seg_bytes + (size_t)d->shard_vecs * 16 + (size_t)nt * d->n_pairs * dense_row;
+            if (walk_table_wanted(ix)) {
+                std::vector<WalkTile> wt(nt);
+                fill_walk_tiles(ix, (uint64_t)(uintptr_t)d->d_seg_ptr, (uint64_t)(uintptr_t)d->d_postings,
+                                (uint64_t)(uintptr_t)d->d_dense, d->n_pairs, wt.data());
+                if (hipMalloc(&d->d_walk, nt * sizeof(WalkTile)) != hipSuccess ||
+                    hipMemcpy(d->d_walk, wt.data(), nt * sizeof(WalkTile), hipMemcpyHostToDevice) != hipSuccess) {
+                    set_error("upload of the per-tile table failed");
+                    return fail(MSR_E_HIP);
+                }
+            }
         } else {
             // Term-range shard: segments are term-ordered inside a tile, so the owned terms of tile t are ONE slice
             // [sp[t][lo], sp[t][hi]) of its postings. The slices are packed back to back, and the segment table keeps
@@ -312,6 +389,7 @@ void device_detach(msr_index* ix) {
     if (d->d_seg_ptr) (void)hipFree(d->d_seg_ptr);
     if (d->d_postings) (void)hipFree(d->d_postings);
     if (d->d_dense) (void)hipFree(d->d_dense);
+    if (d->d_walk) (void)hipFree(d->d_walk);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
     ix->dev = nullptr;
@@ -769,6 +847,34 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
     // top-k. (A launch holds at most 65535 tiles in y; x = queries.)
     int rc = MSR_OK;
     const uint32_t nt = ix->shard_ntiles;
+    if (walk_route(d->d_walk != nullptr, sa.light != 0, b->unsorted_ok, (uint32_t)b->nq, (uint32_t)k)) {
+        // small index, many light queries: one workgroup per query walks the tiles and writes the result rows itself
+        // (msr_walk.hpp): no per-tile lists, no merge launch. The whole kernel counts as score time.
+        WalkArgs wa;
+        wa.s = sa;
+        wa.m.lists = nullptr;
+        wa.m.list_stride = 0;
+        wa.m.n_lists = 0;
+        wa.m.nq = (uint32_t)b->nq;
+        wa.m.k = (uint32_t)k;
+        wa.m.out_keys = b->d_keys;
+        wa.m.out_ord = final_arrays ? b->d_ord : nullptr;
+        wa.m.out_score_u32 = b->d_su32;
+        wa.m.out_score = b->d_sf32;
+        wa.m.out_n = b->d_n;
+        wa.tiles = d->d_walk;
+        wa.n_tiles = nt;
+        rc = launch_walk(d->stream, h->tile_docs, wa);
+        if (rc != MSR_OK) return rc;
+        if (!b->untimed) {
+            HIP_TRY(hipEventRecord(b->ev1, d->stream));
+            HIP_TRY(hipEventRecord(b->ev2, d->stream));
+        }
+        ++b->walks;
+        b->last_k = k;
+        b->timed = !b->untimed;
+        return MSR_OK;
+    }
     uint32_t t1 = nt;
     // (small launches — fewer (tile, query) pairs than one round of resident workgroups — stay in ONE launch: two
     // more kernels in the chain would cost the call more latency than the cheaper selection saves)
@@ -923,7 +1029,8 @@ int msr_batch_debug_stamps(msr_batch* b, unsigned long long out[8]) {
         set_error("msr_batch_debug_stamps: bad argument");
         return MSR_E_INVAL;
     }
-    memset(out, 0, 8 * sizeof(unsigned long long));  // the phase stamps were retired: always zeros
+    memset(out, 0, 8 * sizeof(unsigned long long));  // the phase stamps were retired: zeros ...
+    out[7] = b->walks;  // ... but for the route: searches of this batch that took score_tiles_walk
     return MSR_OK;
 }
 

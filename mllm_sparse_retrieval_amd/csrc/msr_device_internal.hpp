@@ -34,6 +34,14 @@ constexpr size_t kZeroCopyBytes = 64u << 10;  // query block / result block of a
 constexpr uint32_t kSmallMaxPairs = 1024;     // a small call launches at most this many (tile, query) workgroups
 constexpr int kChunkVecs = 64;   // one chunk = one wave-wide uint4 load = 256 postings = 1 KiB
 static_assert(kCandCap >= MSR_KMAX, "candidate buffer must hold k keys");
+// score_tiles_walk (msr_walk.hpp): one workgroup per query walks the handle's tiles. Taken by light batches on handles
+// of 2 .. kWalkMaxTiles tiles (more tiles than that no longer share the L2 between the workgroups in flight, which are
+// spread over all of them), for k <= kWalkMaxK (the running top-k is one wave's worth of keys) and at least
+// kWalkMinQueries queries (one round of resident workgroups: below it, tiles side by side finish a call sooner).
+constexpr uint32_t kWalkMaxTiles = 8;
+constexpr uint32_t kWalkMaxK = 64;
+constexpr uint32_t kWalkMinQueries = 1024;
+constexpr uint32_t kWalkRoundsMask = 7;  // WalkTile::doc0_rounds: doc0 is a multiple of the tile size, rounds <= 4
 
 // ------------------------------------------------------------------------------------------------ tile shapes
 // The launch shape of every kernel that works on one doc tile: <tile, threads, chunk loads per bank, min waves/SIMD of
@@ -76,6 +84,17 @@ inline bool hybrid_tile(uint32_t tile_docs) {  // the tile sizes the hybrid kern
     with_tile_shape(tile_docs, [&](auto s) { yes = s.light; });
     return yes;
 }
+
+// One tile as score_tiles_walk sees it: what score_tiles computes per workgroup from ScoreArgs, built once per handle
+// (fill_walk_tiles) because it depends on the index alone. 32 bytes: one scalar load per tile.
+struct WalkTile {
+    const uint32_t* seg_row;  // the tile's row of seg_ptr
+    const char* post_base;    // address of the tile's first posting vec
+    const char* dense;        // the tile's dense-head rows
+    uint32_t tile_first;      // seg_row[0]
+    uint32_t doc0_rounds;     // first doc ordinal of the tile | rounds of 4*NT accumulators that hold real docs
+};
+static_assert(sizeof(WalkTile) == 32, "one s_load_dwordx8 per tile");
 
 // Caching device allocator of one index handle. msr_search_csr at the reference's call shape (4 queries per call,
 // scripts/search_sparse.sh:16) would otherwise spend more time in hipMalloc / hipFree than in its kernels.
@@ -139,6 +158,7 @@ struct DeviceIndex {
     std::vector<int32_t> pair_local; // index pair p -> resident pair (or -1); identity unless the handle is a term shard
     uint32_t seg_terms = 0;          // terms per row of d_seg_ptr (n_terms, or term_hi - term_lo on a term shard)
     uint32_t term_base = 0;          // query term ids are rebased by this before upload (term_lo on a term shard)
+    WalkTile* d_walk = nullptr;       // [shard_ntiles] tile side of score_tiles_walk, or null: the handle never walks
     uint64_t resident_bytes = 0;     // d_seg_ptr + d_postings + d_dense
     uint32_t vec_base = 0;
     uint64_t shard_vecs = 0;
@@ -231,6 +251,19 @@ struct MergeArgs {
     int32_t* out_n;
 };
 
+struct WalkArgs {
+    ScoreArgs s;            // the query side and n_pairs (the tile side comes from `tiles`)
+    MergeArgs m;            // the result rows (lists / list_stride / n_lists unused)
+    const WalkTile* tiles;  // [n_tiles]
+    uint32_t n_tiles;
+};
+
+// The routing rule of batch_search_local: does a search of `nq` queries at depth k take score_tiles_walk? `has_table`:
+// the handle holds a WalkTile table (2 .. kWalkMaxTiles tiles of 4096 or 8192 docs, every term resident).
+inline bool walk_route(bool has_table, bool light_batch, bool list_as_set, uint32_t nq, uint32_t k) {
+    return has_table && light_batch && !list_as_set && k <= kWalkMaxK && nq >= kWalkMinQueries;
+}
+
 // defined in msr_device.hip
 int launch_select(hipStream_t st, uint32_t tile_docs, const SelectArgs& a);
 int launch_merge(hipStream_t st, const MergeArgs& a);
@@ -270,6 +303,7 @@ struct msr_batch {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;  // the current call's events (borrowed from `events`)
     std::vector<hipEvent_t> events;  // 3 per recorded search call since the last timing reset
     size_t calls = 0;                // recorded calls
+    uint64_t walks = 0;              // searches of this batch that took score_tiles_walk (msr_batch_debug_stamps)
     bool timed = false;
 };
 

@@ -23,6 +23,27 @@
 
 namespace msr {
 
+// The result rows of query q from one wave whose lanes hold at most 64 unique keys `me` (0 = none) and their ranks:
+// the non-empty keys take ranks 0 .. n-1, slots [min(n, k), k) are written as empty. (The tail of merge_wave and of
+// score_tiles_walk: one rule for what a result row holds.)
+__device__ __forceinline__ void emit_ranked(const MergeArgs& a, const uint32_t q, const uint32_t lane, const uint64_t me,
+                                            const uint32_t rank) {
+    const uint32_t n_hit = min((uint32_t)__popcll(__ballot(me != 0)), a.k);
+    const uint64_t o = (uint64_t)q * a.k;
+    auto emit = [&](uint32_t i, uint64_t key) {
+        if (a.out_keys) a.out_keys[o + i] = key;
+        if (a.out_ord) {
+            const uint32_t sc = (uint32_t)(key >> 32);
+            a.out_ord[o + i] = key ? 0xFFFFFFFFu - (uint32_t)key : 0xFFFFFFFFu;
+            a.out_score_u32[o + i] = sc;
+            a.out_score[o + i] = (float)sc;  // round-to-nearest-even, exact below 2^24 (contract T5)
+        }
+    };
+    if (me != 0 && rank < a.k) emit(rank, me);
+    if (lane >= n_hit && lane < a.k) emit(lane, 0ull);
+    if (lane == 0 && a.out_n) a.out_n[q] = (int32_t)n_hit;
+}
+
 // At most 64 keys per query (e.g. 4 tiles x top-10): one WAVE ranks them, keys in registers, ranks by v_readlane
 // broadcasts — no LDS, no barrier. (merge_small's body.)
 __device__ __forceinline__ void merge_wave(const MergeArgs& a, const uint32_t q, const uint32_t lane) {
@@ -42,21 +63,7 @@ __device__ __forceinline__ void merge_wave(const MergeArgs& a, const uint32_t q,
             rank += o > me;
         }
     }
-    const uint32_t n_hit = min((uint32_t)__popcll(__ballot(me != 0)), a.k);
-    // keys are unique, so the non-empty keys take ranks 0 .. n-1; slots [n_hit, k) are empty
-    const uint64_t o = (uint64_t)q * a.k;
-    auto emit = [&](uint32_t i, uint64_t key) {
-        if (a.out_keys) a.out_keys[o + i] = key;
-        if (a.out_ord) {
-            const uint32_t sc = (uint32_t)(key >> 32);
-            a.out_ord[o + i] = key ? 0xFFFFFFFFu - (uint32_t)key : 0xFFFFFFFFu;
-            a.out_score_u32[o + i] = sc;
-            a.out_score[o + i] = (float)sc;  // round-to-nearest-even, exact below 2^24 (contract T5)
-        }
-    };
-    if (me != 0 && rank < a.k) emit(rank, me);
-    if (lane >= n_hit && lane < a.k) emit(lane, 0ull);
-    if (lane == 0 && a.out_n) a.out_n[q] = (int32_t)n_hit;
+    emit_ranked(a, q, lane, me, rank);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel 1

@@ -70,8 +70,19 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t v
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// a pointer to u32s known to lie in device memory (global loads, never flat ones, whatever the pointer came out of)
+typedef const __attribute__((address_space(1))) uint32_t* global_u32;
+
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
+
+// An empty key slot's value, made where it is stored, behind an opaque copy: the kernels that run a selection per tile
+// of a loop would otherwise carry the constant in a register pair through the whole loop.
+__device__ __forceinline__ uint64_t empty_key() {
+    uint32_t z = 0;
+    asm volatile("" : "+v"(z));
+    return ((uint64_t)z << 32) | z;
+}
 
 // Rank-by-counting over `n` UNIQUE non-zero keys in LDS: key with rank r < k goes to out[r]; slots [n, k) get 0.
 // BITONIC: compile the sort path in (kernel instances for k > 512; the k <= 512 instances of score_tiles sit at the
@@ -118,7 +129,7 @@ __device__ __forceinline__ void rank_and_emit(uint64_t* cand, int n, int k, uint
                 }
             }
             if (lane < n && rank < k) out[rank] = me;
-            for (int i = n + lane; i < k; i += 64) out[i] = 0;
+            for (int i = n + lane; i < k; i += 64) out[i] = empty_key();
         }
         return;
     }
@@ -128,7 +139,7 @@ __device__ __forceinline__ void rank_and_emit(uint64_t* cand, int n, int k, uint
         for (int j = 0; j < n; ++j) rank += cand[j] > me;
         if (rank < k) out[rank] = me;
     }
-    for (int i = n + tidx; i < k; i += NT) out[i] = 0;
+    for (int i = n + tidx; i < k; i += NT) out[i] = empty_key();
 }
 
 struct SelectScratch {
@@ -202,7 +213,7 @@ __device__ __forceinline__ void tile_select(const uint4* a4, uint64_t* cand, uin
         const uint32_t v = wmax[lane];  // 64 group maxima, one per lane, in every wave
         smax = wave_max_u32(v);
         if (smax == 0) {  // nothing matched in this tile
-            for (int i = tid; i < k; i += NT) out[i] = 0;
+            for (int i = tid; i < k; i += NT) out[i] = empty_key();
             return;
         }
         if (k <= NT) {
@@ -308,8 +319,12 @@ __device__ __forceinline__ void tile_select(const uint4* a4, uint64_t* cand, uin
         uint32_t prefix = 0, hi_mask = 0, need = (uint32_t)k;
         // first window = the 8 most significant bits of the tile's maximum (spreads the scores over up to 128 bins),
         // then whole bytes below it; the last window may overlap bits that are already fixed (harmless)
+        // (constants of this rare path are made here, behind an opaque copy: a caller that runs the selection in a loop
+        // would otherwise carry them in registers through its whole loop)
+        uint32_t zero = 0, one = 1;
+        asm volatile("" : "+v"(zero), "+v"(one));
         for (int shift = max(31 - __clz(smax) - 7, 0);; shift = max(shift - 8, 0)) {
-            for (int i = tid; i < 256 * SUB / 4; i += NT) reinterpret_cast<uint4*>(hist)[i] = make_uint4(0, 0, 0, 0);
+            for (int i = tid; i < 256 * SUB / 4; i += NT) reinterpret_cast<uint4*>(hist)[i] = make_uint4(zero, zero, zero, zero);
             __syncthreads();
             for (int r = 0; r < rounds; ++r) {
                 const uint4 x = a4[r * NT + tid];
@@ -317,7 +332,7 @@ __device__ __forceinline__ void tile_select(const uint4* a4, uint64_t* cand, uin
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if ((sc4[e] & hi_mask) == prefix)
-                        atomicAdd(&hist[((sc4[e] >> shift) & 255u) * SUB + (lane & (SUB - 1))], 1u);
+                        atomicAdd(&hist[((sc4[e] >> shift) & 255u) * SUB + (lane & (SUB - 1))], one);
             }
             __syncthreads();
             uint4 hb = make_uint4(0, 0, 0, 0);  // bins 4*lane .. 4*lane+3, summed over their SUB copies

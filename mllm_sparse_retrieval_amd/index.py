@@ -438,6 +438,8 @@ class QueryBatch:
         return n.value, a.value, b.value
 
     def debug_stamps(self):
+        """Eight counters (msr_batch_debug_stamps): zeros but for [7], the searches of this batch that walked the tiles
+        in one workgroup per query."""
         out = np.zeros(8, dtype=np.uint64)
         check(lib().msr_batch_debug_stamps(self._h, ptr(out)))
         return out

@@ -183,6 +183,27 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
                      uint32_t flags, const int64_t* t_ptr, const uint32_t* t_ord, uint32_t* out_doc_w, int64_t out_cap,
                      float ms[1]);
 
+/* ---- doc vectors: "WHAT does this doc hold", every term of listed docs with its stored weight. Counterpart: Lucene's
+ * IndexReader.getTermVector() (pyserini: IndexReader.get_document_vector(docid)), which the reference never calls (none
+ * in src/search.py; its src/sparse_statistic.py re-reads the encoder output for the histograms of stored doc weights).
+ * The index is tile-major inverted, there is no forward index: this call streams the postings of every tile that holds
+ * a listed doc on the device, with kernels of its own, and returns the rows as a doc-major CSR.
+ * t_ord holds n doc ordinals: any count, duplicates allowed, any mix of tiles, every doc of the index in one call is
+ * fine. Listed entry e owns [out_ptr[e], out_ptr[e+1]) of (out_term, out_w): every term the doc holds with its stored
+ * weight (1 .. 65535) in ASCENDING TERM ID; dense-head terms are merged into the same order and cannot be told from
+ * segment terms; a repeated ordinal gets its own equal row. For an index built by msr_index_build_csr from rows sorted
+ * by term, listing ordinal o returns exactly the input row of the doc that got ordinal o.
+ * Sizing as msr_encode_queries: out_ptr (n + 1 entries) and *n_entries are always filled; out_term / out_w are filled
+ * when cap >= *n_entries (call with cap = 0 and null arrays to size).
+ * ms (nullable) = HIP-event times of {count pass, fill pass, ordering pass}; a pass that was not launched reports 0.
+ * Argument errors are reported before the device is looked at: MSR_E_INVAL for a null ix / out_ptr / n_entries, for a
+ * null t_ord with n > 0, n < 0, cap < 0, for null out_term / out_w with cap > 0; MSR_E_RANGE for an ordinal >= n_docs;
+ * MSR_E_INVAL for a doc-range or term-range shard handle; then MSR_E_NODEVICE on a handle opened with device < 0.
+ * n == 0 returns MSR_OK with out_ptr[0] = 0 and no launch. A total of 2^32 entries or more is MSR_E_RANGE (known after
+ * the count pass; out_ptr and *n_entries are filled): split the list. There is no CPU path. */
+int msr_doc_vectors(msr_index* ix, const uint32_t* t_ord, int64_t n, int64_t* out_ptr, uint32_t* out_term, uint32_t* out_w,
+                    int64_t cap, int64_t* n_entries, float ms[3]);
+
 /* Where the calling thread's last msr_search_csr spent its time, in microseconds: {query normalisation + device buffers
  * + upload enqueued, kernels enqueued, wait for the stream, download + copy out, release, the whole call, 0, 0}. Slots 6
  * and 7 (once HIP-event spans of the kernels) stay in the ABI and are always 0: the call records no events. The reference

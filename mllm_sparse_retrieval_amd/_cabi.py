@@ -64,6 +64,7 @@ SYMBOLS = [
     ("msr_search_csr", _I, [_VP, _VP, _VP, _VP, _I, _I, _U32, _VP, _VP, _VP, _VP]),
     ("msr_rank_docs", _I, [_VP, _VP, _VP, _VP, _I, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_explain_docs", _I, [_VP, _VP, _VP, _VP, _I, _U32, _VP, _VP, _VP, C.c_int64, _VP]),
+    ("msr_doc_vectors", _I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP]),
     ("msr_search_laps", _I, [_VP]),
     ("msr_search_text", _I, [_VP, _VP, _I, _I, _U32, _VP, _VP, _VP, _VP]),
     ("msr_encode_queries", _I, [_VP, _VP, _I, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),

@@ -10,6 +10,9 @@
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
            [--ranks: exact rank of every judged row at any depth (msr_dense_rank_rows) -> the same metrics, dense.ranks.tsv]
 
+    python -m mllm_sparse_retrieval_amd vectors --sparse_index out/ [--docids a,b,c | --docids_file F] [--output FILE]
+           (the stored doc vectors back out of the index, jsonl in the encode format; no counterpart script)
+
     python -m mllm_sparse_retrieval_amd eval   --runs_dir runs/ --qrels out/qrels.csv --dataset_name flickr \
            --query_type text [--compat-denominator --world_size 4]                                (recall of TREC runs)
 
@@ -87,6 +90,50 @@ def _cmd_index(a):
     t0 = time.time()
     path = build_index_from_jsonl(a.input, out, threads=a.threads, tile_docs=a.tile_docs)
     print(f"index: {path} ({os.path.getsize(path) / 1e6:.1f} MB) in {time.time() - t0:.2f}s")
+
+
+def _cmd_vectors(a):
+    """Doc vectors out of the index (msr_doc_vectors) as jsonl in the encode format (src/encode.py:351-359)."""
+    import numpy as np
+
+    from .index import SparseIndex, index_file_of
+
+    if a.docids is not None and a.docids_file is not None:
+        sys.exit("vectors: give --docids or --docids_file, not both")
+    out = a.output or os.path.join(a.sparse_index if os.path.isdir(a.sparse_index) else os.path.dirname(a.sparse_index),
+                                   "vectors.jsonl")
+    with SparseIndex(index_file_of(a.sparse_index), device=a.device) as ix:
+        if a.docids is None and a.docids_file is None:
+            # every doc, whole tiles at a time; a chunk is sized by the average row to stay well below 2^32 entries
+            ords = np.arange(ix.n_docs, dtype=np.uint32)
+            avg = max(1, -(-ix.n_postings // max(1, ix.n_docs)))
+            chunk = ix.tile_docs * max(1, (1 << 26) // (avg * ix.tile_docs))
+        else:
+            if a.docids is not None:
+                ids = [d for d in a.docids.split(",") if d]
+            else:
+                with open(a.docids_file, encoding="utf-8") as f:
+                    ids = [ln.strip() for ln in f if ln.strip()]
+            ord_of = {d: o for o, d in enumerate(ix.docid_table().tolist())}
+            unknown = [d for d in ids if d not in ord_of]
+            if unknown:
+                print(f"vectors: not in the index: {', '.join(unknown)}", file=sys.stderr)
+            ords = np.asarray([ord_of[d] for d in ids if d in ord_of], dtype=np.uint32)
+            chunk = 1 << 16
+        toks, n_entries = {}, 0
+        with open(out, "w", encoding="utf-8") as f:
+            for c0 in range(0, len(ords), chunk):
+                part = ords[c0:c0 + chunk]
+                d_ptr, term, weight = ix.doc_vectors(part)
+                n_entries += len(term)
+                for t in np.unique(term).tolist():
+                    if t not in toks:
+                        toks[t] = ix.term_str(t)
+                d_ptr, term, weight = d_ptr.tolist(), term.tolist(), weight.tolist()
+                for e, docid in enumerate(ix.docids(part)):
+                    vec = {toks[term[j]]: weight[j] for j in range(d_ptr[e], d_ptr[e + 1])}
+                    f.write(json.dumps(dict(id=docid, content="", vector=vec)) + "\n")
+    print(f"Doc vectors: {len(ords)} docs, {n_entries} entries -> {out}")
 
 
 def read_queries(path):
@@ -645,6 +692,15 @@ def main(argv=None):
     v.add_argument("--world_size", type=int, default=4, help="ranks to replay with --compat-denominator "
                                                              "(scripts/search_sparse.sh:14 uses 4)")
     v.set_defaults(fn=_cmd_eval)
+
+    d = sub.add_parser("vectors", help="doc vectors out of the index as jsonl in the encode format (every doc, or the "
+                                       "listed ones), read on the GPU by msr_doc_vectors")
+    d.add_argument("--sparse_index", required=True)
+    d.add_argument("--docids", default=None, help="comma-separated external doc ids (default: every doc, in ordinal order)")
+    d.add_argument("--docids_file", default=None, help="one external doc id per line")
+    d.add_argument("--output", default=None, help="default: <sparse_index>/vectors.jsonl")
+    d.add_argument("--device", type=int, default=0)
+    d.set_defaults(fn=_cmd_vectors)
 
     a = ap.parse_args(argv)
     a.fn(a)

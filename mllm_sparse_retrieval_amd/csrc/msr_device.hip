@@ -14,6 +14,7 @@
 #include "msr_walk.hpp"
 #include "msr_rank.hpp"
 #include "msr_explain.hpp"
+#include "msr_doc_vectors.hpp"
 
 namespace msr {
 
@@ -140,6 +141,36 @@ static int launch_explain(hipStream_t st, uint32_t tile_docs, uint32_t n_pairs, 
         const bool known = with_tile_shape(
             tile_docs, [&](auto s) { hipLaunchKernelGGL((explain_tiles<decltype(s)::docs>), grid, dim3(256), 0, st, a); });
         if (!known) return no_tile_shape(tile_docs);
+        HIP_TRY(hipGetLastError());
+    }
+    return MSR_OK;
+}
+
+// One pass of msr_doc_vectors (msr_doc_vectors.hpp), the count pass or (fill) the fill pass: docvec_tiles over work items
+// [0, n_work) of a0.work, then docvec_dense over rows [0, a0.n_rows) when the index has a dense head. 1-D grids, sliced at
+// the gather's grid limit.
+static int launch_docvec(hipStream_t st, bool fill, uint32_t n_work, const DocvecArgs& a0) {
+    for (uint32_t o0 = 0; o0 < n_work; o0 += kRankMaxGridX) {
+        DocvecArgs a = a0;
+        a.work = a0.work + o0;
+        const dim3 grid(std::min<uint32_t>(kRankMaxGridX, n_work - o0));
+        const bool known = with_tile_shape(a.tile_docs, [&](auto s) {
+            if (fill)
+                hipLaunchKernelGGL((docvec_tiles<decltype(s)::docs, true>), grid, dim3(256), 0, st, a);
+            else
+                hipLaunchKernelGGL((docvec_tiles<decltype(s)::docs, false>), grid, dim3(256), 0, st, a);
+        });
+        if (!known) return no_tile_shape(a.tile_docs);
+        HIP_TRY(hipGetLastError());
+    }
+    for (uint32_t r0 = 0; a0.n_pairs != 0 && r0 < a0.n_rows; r0 += kRankMaxGridX) {  // (256 rows per workgroup)
+        DocvecArgs a = a0;
+        a.row0 = r0;
+        const dim3 grid((std::min<uint32_t>(kRankMaxGridX, a0.n_rows - r0) + 255) / 256);
+        if (fill)
+            hipLaunchKernelGGL(docvec_dense<true>, grid, dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL(docvec_dense<false>, grid, dim3(256), 0, st, a);
         HIP_TRY(hipGetLastError());
     }
     return MSR_OK;
@@ -1366,6 +1397,158 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
         const uint32_t q = (uint32_t)(std::upper_bound(t_ptr, t_ptr + nq + 1, (int64_t)dp.first) - t_ptr - 1);
         memcpy(out_doc_w + pl.x_off[dp.first], out_doc_w + pl.x_off[dp.second], (size_t)(q_ptr[q + 1] - q_ptr[q]) * 4);
     }
+    cs.ok = true;
+    return MSR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ doc vectors
+int msr_doc_vectors(msr_index* ix, const uint32_t* t_ord, int64_t n, int64_t* out_ptr, uint32_t* out_term, uint32_t* out_w,
+                    int64_t cap, int64_t* n_entries, float ms[3]) {
+    const char* const who = "msr_doc_vectors";
+    // ---- checks
+    if (!ix || !out_ptr || !n_entries) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if (n < 0 || cap < 0 || (n > 0 && !t_ord)) {
+        set_error("%s: %s", who, n < 0 ? "n is negative" : cap < 0 ? "cap is negative" : "null t_ord");
+        return MSR_E_INVAL;
+    }
+    if (cap > 0 && (!out_term || !out_w)) {
+        set_error("%s: null output arrays with cap = %lld", who, (long long)cap);
+        return MSR_E_INVAL;
+    }
+    const IndexHeader* h = ix->host.h;
+    for (int64_t e = 0; e < n; ++e)
+        if ((uint64_t)t_ord[e] >= h->n_docs) {
+            set_error("%s: ordinal %u (entry %lld) is outside the index (%llu docs)", who, t_ord[e], (long long)e,
+                      (unsigned long long)h->n_docs);
+            return MSR_E_RANGE;
+        }
+    if (ix->term_nshards > 0 || ix->shard_ntiles != h->n_tiles) {
+        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
+                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU path to the doc vectors");
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+    out_ptr[0] = 0;
+    *n_entries = 0;
+    if (n == 0) return MSR_OK;
+    DeviceIndex* d = ix->dev;
+    CallScratch cs(d);
+    // ---- plan: the distinct listed docs in ordinal order (the rows of the device output), (tile, stripe) work items
+    DocvecPlan pl;
+    docvec_plan(ix->host.seg_ptr, h->n_terms, h->tile_docs, t_ord, n, pl);
+    const uint32_t rows = (uint32_t)pl.ords.size(), n_work = (uint32_t)(pl.work.size() / 4);
+    // ---- upload, one block: work items (uint4) | row ordinals | dense-head terms
+    const size_t o_work = cs.put(pl.work), o_ords = cs.put(pl.ords), o_dt = cs.put(ix->host.dense_terms, h->n_dense);
+    const size_t in_bytes = cs.in.size() * 4, len_bytes = (size_t)rows * 4, ptr_bytes = ((size_t)rows + 1) * 4;
+    uint32_t *d_in = cs.alloc(in_bytes), *d_len = cs.alloc(len_bytes), *d_ptr = cs.alloc(ptr_bytes);
+    if (!d_in || !d_len || !d_ptr) {
+        set_error("%s: device allocation failed (%zu bytes of row lengths)", who, len_bytes);
+        return MSR_E_NOMEM;
+    }
+    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return MSR_E_HIP;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // count | fill | ordering, the host's part between
+    for (int i = 0; ms && i < 5; ++i)
+        if (!(ev[i] = cs.event())) {
+            set_error("%s: hipEventCreate failed", who);
+            return MSR_E_HIP;
+        }
+    DocvecArgs va;
+    va.seg_ptr = d->d_seg_ptr;
+    va.postings = d->d_postings;
+    va.dense = d->d_dense;
+    va.dense_terms = d_in + o_dt;
+    va.n_pairs = d->n_pairs;
+    va.n_terms = d->seg_terms;
+    va.vec_base = d->vec_base;
+    va.tile_docs = h->tile_docs;
+    va.work = reinterpret_cast<const uint4*>(d_in + o_work);
+    va.row0 = 0;
+    va.n_rows = rows;
+    va.ords = d_in + o_ords;
+    va.len = d_len;
+    va.ptr = d_ptr;
+    va.term = va.w = va.out_term = va.out_w = nullptr;
+    // ---- count pass; the row lengths come back and are prefix-summed on the host
+    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if (!hip_ok(who, hipMemsetAsync(d_len, 0, len_bytes, d->stream), "hipMemsetAsync")) return MSR_E_HIP;
+    int rc = launch_docvec(d->stream, false, n_work, va);
+    if (rc != MSR_OK) return rc;
+    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    std::vector<uint32_t> row_ptr((size_t)rows + 1, 0u);  // (lengths first, then the exclusive prefix sum)
+    if (!hip_ok(who, hipStreamSynchronize(d->stream), "the count pass") ||
+        !hip_ok(who, hipMemcpy(row_ptr.data() + 1, d_len, len_bytes, hipMemcpyDeviceToHost), "download of the row lengths"))
+        return MSR_E_HIP;
+    if (ms && !hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime")) return MSR_E_HIP;
+    uint64_t total = 0;
+    for (int64_t e = 0; e < n; ++e) {
+        total += row_ptr[(size_t)pl.row_of[(size_t)e] + 1];
+        out_ptr[e + 1] = (int64_t)total;
+    }
+    *n_entries = (int64_t)total;
+    if (total >= (1ull << 32)) {
+        set_error("%s: the listed docs hold %llu entries, more than one call serves (split the list)", who,
+                  (unsigned long long)total);
+        return MSR_E_RANGE;
+    }
+    if ((uint64_t)cap < total || total == 0) {  // the sizing call, or nothing to fill
+        cs.ok = true;
+        return MSR_OK;
+    }
+    for (uint32_t r = 0; r < rows; ++r) row_ptr[(size_t)r + 1] += row_ptr[r];  // (<= total: every row is listed)
+    const uint32_t n_dev = row_ptr[rows];
+    // ---- fill pass (fill order) and ordering pass (ascending term id), out of place
+    const size_t arr_bytes = (size_t)n_dev * 4;
+    uint32_t *d_t = cs.alloc(arr_bytes), *d_w = cs.alloc(arr_bytes), *d_ot = cs.alloc(arr_bytes), *d_ow = cs.alloc(arr_bytes);
+    if (!d_t || !d_w || !d_ot || !d_ow) {
+        set_error("%s: device allocation failed (4 x %zu bytes of doc vectors)", who, arr_bytes);
+        return MSR_E_NOMEM;
+    }
+    va.term = d_t;
+    va.w = d_w;
+    va.out_term = d_ot;
+    va.out_w = d_ow;
+    if (!hip_ok(who, hipMemcpyAsync(d_ptr, row_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, d->stream), "upload of the row starts") ||
+        !hip_ok(who, hipMemsetAsync(d_len, 0, len_bytes, d->stream), "hipMemsetAsync"))
+        return MSR_E_HIP;
+    if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    rc = launch_docvec(d->stream, true, n_work, va);
+    if (rc != MSR_OK) return rc;
+    if (ms && !hip_ok(who, hipEventRecord(ev[3], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    for (uint32_t r0 = 0; r0 < rows; r0 += kRankMaxGridX) {
+        va.row0 = r0;
+        hipLaunchKernelGGL(docvec_order, dim3(std::min<uint32_t>(kRankMaxGridX, rows - r0)), dim3(256), 0, d->stream, va);
+        if (!hip_ok(who, hipGetLastError(), "docvec_order")) return MSR_E_HIP;
+    }
+    if (ms && !hip_ok(who, hipEventRecord(ev[4], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    // ---- download: straight into the caller's arrays when the list is the rows (ascending, no duplicate), else row by row
+    if (!hip_ok(who, hipStreamSynchronize(d->stream), "the fill and ordering passes")) return MSR_E_HIP;
+    bool same = rows == (uint64_t)n;
+    for (int64_t e = 0; same && e < n; ++e) same = pl.row_of[(size_t)e] == (uint32_t)e;
+    std::vector<uint32_t> ht, hw;
+    if (!same) {
+        ht.resize(n_dev);
+        hw.resize(n_dev);
+    }
+    if (!hip_ok(who, hipMemcpy(same ? out_term : ht.data(), d_ot, arr_bytes, hipMemcpyDeviceToHost), "download") ||
+        !hip_ok(who, hipMemcpy(same ? out_w : hw.data(), d_ow, arr_bytes, hipMemcpyDeviceToHost), "download"))
+        return MSR_E_HIP;
+    for (int64_t e = 0; !same && e < n; ++e) {
+        const uint32_t r = pl.row_of[(size_t)e];
+        const size_t len = (size_t)(row_ptr[(size_t)r + 1] - row_ptr[r]);
+        if (len == 0) continue;
+        memcpy(out_term + out_ptr[e], ht.data() + row_ptr[r], len * 4);
+        memcpy(out_w + out_ptr[e], hw.data() + row_ptr[r], len * 4);
+    }
+    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[1], ev[2], ev[3]), "hipEventElapsedTime") ||
+               !hip_ok(who, hipEventElapsedTime(&ms[2], ev[3], ev[4]), "hipEventElapsedTime")))
+        return MSR_E_HIP;
     cs.ok = true;
     return MSR_OK;
 }

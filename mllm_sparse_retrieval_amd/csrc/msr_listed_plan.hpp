@@ -1,7 +1,8 @@
-// Host side of the listed-docs calls msr_rank_docs and msr_explain_docs (plain C++, no HIP; included by msr_rank.hpp and
-// msr_explain.hpp): the tables their kernels read, built from the caller's CSR arrays after the argument checks and the
-// search path's query normalisation have passed (every term id of a counting entry is below n_terms, every ordinal below
-// n_docs, at most MSR_RANK_MAX_TARGETS / MSR_EXPLAIN_MAX_TARGETS listed docs per query, fewer than 2^32 output slots).
+// Host side of the listed-docs calls msr_rank_docs, msr_explain_docs and msr_doc_vectors (plain C++, no HIP; included by
+// msr_rank.hpp, msr_explain.hpp and msr_doc_vectors.hpp): the tables their kernels read, built from the caller's arrays
+// after the argument checks and, for the two calls that take queries, the search path's query normalisation have passed
+// (every term id of a counting entry is below n_terms, every ordinal below n_docs, at most MSR_RANK_MAX_TARGETS /
+// MSR_EXPLAIN_MAX_TARGETS listed docs per query, fewer than 2^32 output slots).
 #pragma once
 
 #include <algorithm>
@@ -127,6 +128,40 @@ inline void explain_plan(const HostIndex& hx, const int64_t* q_ptr, const int32_
         }
     }
     group_pairs(its, pl.pairs, pl.items);
+}
+
+// ------------------------------------------------------------------------------------------------ msr_doc_vectors
+constexpr uint32_t kDocvecStripeVecs = 8192;  // vecs (128 KiB of postings) one workgroup of docvec_tiles streams
+constexpr uint32_t kDocvecSortRow = 2048;     // longest row docvec_order sorts on chip; longer rows are placed by counting
+
+struct DocvecPlan {
+    std::vector<uint32_t> ords;    // [rows] the distinct listed ordinals, ascending: row r of the device output
+    std::vector<uint32_t> row_of;  // [n] row of listed entry e
+    std::vector<uint32_t> work;    // [][4] {tile, first row, rows, stripe of the tile's vec range}, tile-major
+};
+
+// seg_ptr: the index's [n_tiles][n_terms + 1] table (absolute vec indexes); every ordinal is below n_docs.
+inline void docvec_plan(const uint32_t* seg_ptr, uint32_t n_terms, uint32_t tile, const uint32_t* t_ord, int64_t n,
+                        DocvecPlan& pl) {
+    pl.ords.assign(t_ord, t_ord + n);
+    std::sort(pl.ords.begin(), pl.ords.end());
+    pl.ords.erase(std::unique(pl.ords.begin(), pl.ords.end()), pl.ords.end());
+    pl.row_of.resize((size_t)n);
+    for (int64_t e = 0; e < n; ++e)
+        pl.row_of[(size_t)e] = (uint32_t)(std::lower_bound(pl.ords.begin(), pl.ords.end(), t_ord[e]) - pl.ords.begin());
+    const size_t rows = pl.ords.size();
+    for (size_t r0 = 0; r0 < rows;) {
+        const uint32_t t = pl.ords[r0] / tile;
+        size_t r1 = r0 + 1;
+        while (r1 < rows && pl.ords[r1] / tile == t) ++r1;
+        const uint32_t* sp = seg_ptr + (uint64_t)t * ((uint64_t)n_terms + 1);
+        const uint32_t vecs = sp[n_terms] - sp[0];  // a tile without a vec (dense head only) gets no stripe
+        for (uint32_t s = 0; (uint64_t)s * kDocvecStripeVecs < vecs; ++s) {
+            const uint32_t row[4] = {t, (uint32_t)r0, (uint32_t)(r1 - r0), s};
+            pl.work.insert(pl.work.end(), row, row + 4);
+        }
+        r0 = r1;
+    }
 }
 
 }  // namespace msr

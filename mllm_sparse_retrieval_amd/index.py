@@ -250,6 +250,27 @@ class SparseIndex:
                                      C.cast(ms, C.c_void_p) if with_ms else None))
         return (x_ptr, doc_w, float(ms[0])) if with_ms else (x_ptr, doc_w)
 
+    def doc_vectors(self, ords, with_ms=False):
+        """Whole doc vectors of listed docs (msr_doc_vectors): any number of ordinals, duplicates allowed. Returns the
+        doc-major CSR (ptr int64 [n + 1], term uint32, weight uint32): listed entry e owns [ptr[e], ptr[e + 1]), every
+        term the doc holds with its stored weight in ascending term id (dense-head terms merged in). The sizing call is
+        made inside. with_ms=True appends the HIP-event times (count, fill, ordering pass) of the filling call."""
+        ords = np.ascontiguousarray(ords, dtype=np.uint32)
+        if ords.ndim != 1:
+            raise ValueError("ords must be one-dimensional")
+        n = len(ords)
+        d_ptr = np.zeros(n + 1, dtype=np.int64)
+        need = C.c_int64()
+        ms = (C.c_float * 3)()
+        ms_arg = C.cast(ms, C.c_void_p) if with_ms else None
+        check(lib().msr_doc_vectors(self._h, ptr(ords), n, ptr(d_ptr), None, None, 0, C.byref(need), ms_arg))
+        term = np.empty(need.value, dtype=np.uint32)
+        weight = np.empty(need.value, dtype=np.uint32)
+        if need.value:
+            check(lib().msr_doc_vectors(self._h, ptr(ords), n, ptr(d_ptr), ptr(term), ptr(weight), need.value,
+                                        C.byref(need), ms_arg))
+        return (d_ptr, term, weight, tuple(float(x) for x in ms)) if with_ms else (d_ptr, term, weight)
+
     def search_text(self, queries, k, drop_df_eq_n=True):
         """Query strings (tokens repeated `weight` times, src/search.py:419-422) -> the same outputs as search_csr;
         tokenisation, counting and dictionary lookup run in C inside the call."""

@@ -17,6 +17,7 @@ from collections import Counter
 
 import numpy as np
 
+from ._cabi import MSR_KMAX
 from .index import SparseIndex
 
 
@@ -78,25 +79,30 @@ class LuceneImpactSearcher:
         q_ptr, toks, ws = tokenize_queries(queries)
         return q_ptr, self.index.lookup(toks), ws
 
+    def _idf_rule(self, term_ids, ws):
+        """-> (ws, drop_df_eq_n). idf = log(N / df) > min_idf: with the default min_idf = 0 exactly the df == N terms go
+        (contract T3, the flag); a positive min_idf is applied here on the host, by zeroing the weights it filters."""
+        if self.min_idf > 0:
+            df = self.index.df(term_ids).astype(np.float64)
+            with np.errstate(divide="ignore"):
+                idf = np.log(self.index.n_docs / np.maximum(df, 1e-300))
+            ws = np.where((df > 0) & (idf > self.min_idf), ws, 0).astype(np.int32)
+            return ws, True if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        return ws, self.min_idf >= 0 if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+
     def search(self, q, k=10):
         return self.batch_search([q], ["_q"], k)["_q"]
 
     def batch_search(self, queries, qids, k=10, threads=1, fields=None):
         if len(queries) != len(qids):
             raise ValueError("queries and qids differ in length")
-        # idf = log(N/df) > min_idf: with the default min_idf = 0 exactly the df == N terms go (contract T3);
-        # a positive min_idf is applied here on the host (Python tokenisation), everything else tokenises in C.
+        # a positive min_idf needs the term ids on this side (Python tokenisation), everything else tokenises in C
         if self.min_idf > 0:
             q_ptr, term_ids, ws = self._encode(queries)
-            df = self.index.df(term_ids).astype(np.float64)
-            with np.errstate(divide="ignore"):
-                idf = np.log(self.index.n_docs / np.maximum(df, 1e-300))
-            ws = np.where((df > 0) & (idf > self.min_idf), ws, 0).astype(np.int32)
-            drop = True if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+            ws, drop = self._idf_rule(term_ids, ws)
             ords, scores, _, n = self.index.search_csr(q_ptr, term_ids, ws, k, drop_df_eq_n=drop)
         else:
-            drop = self.min_idf >= 0 if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
-            ords, scores, _, n = self.index.search_text(queries, k, drop_df_eq_n=drop)
+            ords, scores, _, n = self.index.search_text(queries, k, drop_df_eq_n=self._idf_rule(None, None)[1])
         out = {}
         table = self.index.docid_table() if len(qids) * k > 64 else None
         score_rows = scores.tolist()
@@ -118,16 +124,8 @@ class LuceneImpactSearcher:
         if getattr(self, "_ord_of", None) is None:
             self._ord_of = {d: o for o, d in enumerate(table.tolist())}
         ord_of = self._ord_of
-        if self.min_idf > 0:  # as in batch_search: the idf filter on the host
-            q_ptr, term_ids, ws = self._encode(queries)
-            df = self.index.df(term_ids).astype(np.float64)
-            with np.errstate(divide="ignore"):
-                idf = np.log(self.index.n_docs / np.maximum(df, 1e-300))
-            ws = np.where((df > 0) & (idf > self.min_idf), ws, 0).astype(np.int32)
-            drop = True if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
-        else:
-            q_ptr, term_ids, ws = self.index.encode_queries(queries)
-            drop = self.min_idf >= 0 if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        q_ptr, term_ids, ws = self._encode(queries) if self.min_idf > 0 else self.index.encode_queries(queries)
+        ws, drop = self._idf_rule(term_ids, ws)
         t_ptr, t_ord = [0], []
         for tg in targets:
             t_ord.extend(ord_of[str(d)] for d in tg if str(d) in ord_of)
@@ -166,14 +164,7 @@ class LuceneImpactSearcher:
         ord_of = self._ord_of
         q_ptr, toks, ws = tokenize_queries(queries)  # (the tokens name the rows, so they are kept on this side)
         term_ids = self.index.lookup(toks)
-        if self.min_idf > 0:  # as in batch_rank: the idf filter on the host
-            df = self.index.df(term_ids).astype(np.float64)
-            with np.errstate(divide="ignore"):
-                idf = np.log(self.index.n_docs / np.maximum(df, 1e-300))
-            ws = np.where((df > 0) & (idf > self.min_idf), ws, 0).astype(np.int32)
-            drop = True if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
-        else:
-            drop = self.min_idf >= 0 if self.drop_df_eq_n is None else bool(self.drop_df_eq_n)
+        ws, drop = self._idf_rule(term_ids, ws)
         t_ptr, t_ord = [0], []
         for tg in targets:
             t_ord.extend(ord_of[str(d)] for d in tg if str(d) in ord_of)
@@ -193,3 +184,50 @@ class LuceneImpactSearcher:
                     row.append((d, None, None))
             out[qid] = row
         return out
+
+    def _ords_of(self, docids):
+        """External doc ids -> (known ids as strings in the given order, their ordinals uint32)."""
+        if getattr(self, "_ord_of", None) is None:
+            self._ord_of = {d: o for o, d in enumerate(self.index.docid_table().tolist())}
+        known = [str(d) for d in docids if str(d) in self._ord_of]
+        return known, np.asarray([self._ord_of[d] for d in known], dtype=np.uint32)
+
+    def batch_doc_vectors(self, docids):
+        """What named docs hold: {docid: {token: weight}} with the tokens in ascending term id, None for an id the index
+        does not hold. Counterpart: pyserini's IndexReader.get_document_vector(docid), which the reference never calls;
+        the vectors are read out of the inverted index on the GPU (SparseIndex.doc_vectors)."""
+        known, ords = self._ords_of(docids)
+        d_ptr, term, weight = self.index.doc_vectors(ords)
+        toks = {t: self.index.term_str(t) for t in np.unique(term).tolist()}
+        d_ptr, term, weight = d_ptr.tolist(), term.tolist(), weight.tolist()
+        by_str = {}
+        for e, d in enumerate(known):
+            by_str[d] = {toks[term[j]]: weight[j] for j in range(d_ptr[e], d_ptr[e + 1])}
+        return {d: by_str.get(str(d)) for d in docids}
+
+    def batch_search_docs(self, docids, k=10, remove_self=True):
+        """Search with docs of the index as the queries: {docid: [Hit, ...]}, None for an id the index does not hold.
+        The query of a doc is its stored vector (its terms, its weights as query weights), under the searcher's own
+        drop_df_eq_n / min_idf rule; MSR_E_OVERFLOW / MSR_E_RANGE refusals of the search are passed on. With remove_self
+        the search runs at k + 1 and the doc itself is dropped (so k <= MSR_KMAX - 1). Host glue over
+        SparseIndex.doc_vectors and search_csr."""
+        depth = k + 1 if remove_self else k
+        if k < 1 or depth > MSR_KMAX:
+            raise ValueError(f"k = {k} is outside 1 .. {MSR_KMAX - 1 if remove_self else MSR_KMAX}"
+                             + (" (remove_self searches at k + 1)" if remove_self else ""))
+        known, ords = self._ords_of(docids)
+        if not known:
+            return {d: None for d in docids}
+        d_ptr, term, weight = self.index.doc_vectors(ords)
+        term_ids, ws = term.astype(np.int32), weight.astype(np.int32)
+        ws, drop = self._idf_rule(term_ids, ws)
+        res_ord, scores, _, n = self.index.search_csr(d_ptr, term_ids, ws, depth, drop_df_eq_n=drop)
+        table = self.index.docid_table()
+        by_str = {}
+        for i, d in enumerate(known):
+            cnt = int(n[i])
+            row_o, row_s = res_ord[i, :cnt], scores[i, :cnt].tolist()
+            keep = [j for j in range(cnt) if not (remove_self and int(row_o[j]) == int(ords[i]))][:k]
+            ids = table[row_o].tolist()
+            by_str[d] = [Hit(ids[j], row_s[j]) for j in keep]
+        return {d: by_str.get(str(d)) for d in docids}

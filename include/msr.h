@@ -128,6 +128,32 @@ int msr_search_csr(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, c
                    uint32_t flags, uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32,
                    int32_t* out_n);
 
+/* ---- deep lists: the plain ranked list beyond MSR_KMAX, "the best 2 000 / 5 000 / 10 000 docs of every query". The
+ * reference treats depth as a free integer (src/arguments.py:59, passed into batch_search at src/search.py:57,86);
+ * rerankers, pooling and MedR-style analysis consume such lists. MSR_DEEP_KMAX is 16 384 because one row of 16 384
+ * composite u64 keys is 128 KiB: it fits one workgroup's LDS on gfx950 (160 KiB per CU), so a single in-LDS sort is
+ * possible. The scoring is the search's own accumulation (the exact u32 scores of every doc, dumped per tile); one
+ * kernel, deep_select_rows, then takes the exact top-k of each query's score row.
+ * Queries are CSR and normalised exactly as by msr_search_csr (MSR_F_DROP_DF_EQ_N honoured, the same MSR_E_OVERFLOW /
+ * MSR_E_RANGE refusals). 1 <= k <= MSR_DEEP_KMAX, anything else is MSR_E_RANGE; k may exceed n_docs. Outputs are
+ * row-major [nq][k] with the meaning and the padding of msr_search_csr: hits are the docs with score > 0, ordered by
+ * score descending, lower ordinal first; out_n[i] = min(k, hits); slots past out_n[i] hold 0xFFFFFFFF / 0 / 0.f; the f32
+ * score is (float)u32, round to nearest even. out_score_u32 may be NULL.
+ * IDENTITIES: for k <= MSR_KMAX every output array is bit-equal to msr_search_csr at that k; for any k, columns
+ * [0, min(k, 1024)) equal the search at k = 1024; the doc at column c < out_n[i] of row i has rank c + 1 from
+ * msr_rank_docs on the same inputs with self_ord NULL.
+ * Only a whole-index handle is served (doc-range and term-range shard handles: MSR_E_INVAL, as for msr_rank_docs); all
+ * five tile sizes, with or without a dense head. ms (nullable) = HIP-event times summed over the passes of queries (the
+ * score rows of one pass stay at or below 256 MiB): {the scoring launches, the deep selection}.
+ * Argument errors are reported before any device work: MSR_E_INVAL for a null ix / q_ptr / out_doc_ord / out_score /
+ * out_n, nq < 0 and a shard handle; then MSR_E_RANGE for k; then MSR_E_NODEVICE on a handle opened with device < 0 (the
+ * CSR arrays themselves are checked with the normalisation, as by msr_search_csr). nq == 0 returns MSR_OK without a
+ * launch. Measured against the staged search at k = 1000: DESIGN.md §5. */
+#define MSR_DEEP_KMAX 16384 /* largest k of the deep calls */
+int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int k,
+                    uint32_t flags, uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32, int32_t* out_n,
+                    float ms[2]);
+
 /* ---- exact ranks of listed docs: "where does this doc stand for this query", at any depth. Stands beside the ranked
  * lists the reference reads its hits from (src/search.py:86-99) and the recall counting over them (src/metrices.py);
  * there is NO counterpart call in the reference or in pyserini: a judged doc below the search depth is simply missing
@@ -349,6 +375,21 @@ int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t*
 #define MSR_DENSE_RANK_MAX_TARGETS 64 /* listed rows per query */
 int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, const int64_t* t_ptr, const uint32_t* t_row,
                         const int32_t* self_row, uint32_t* out_rank, uint32_t* out_key, float ms[2]);
+/* Deep lists on the dense route: the dense search for 1 <= k <= MSR_DEEP_KMAX (else MSR_E_RANGE). Serves both handle
+ * kinds: q is [nq][h] in the handle's precision and q_is_f32 must match the handle (else MSR_E_INVAL), as in
+ * msr_dense_rank_rows. The passes and the GEMM are those of msr_dense_search / msr_dense_search_f32, so on an fp16 handle
+ * the same query matrix gives the same keys; the exact top-k of every key row is then taken by deep_select_rows instead
+ * of the tile selection and merge. Outputs ([nq][k] row indices and keys, out_n), the key map, the padding (0xFFFFFFFF /
+ * 0) and the tie rule (lower ROW) are those of msr_dense_search; every row is a hit, so out_n[i] = min(k, n).
+ * IDENTITIES: for k <= MSR_KMAX the outputs are bit-equal to the search at that k on the same query matrix; for any k,
+ * columns [0, min(k, 1024)) equal the search at k = 1024; the row at column c of query i has rank c + 1 from
+ * msr_dense_rank_rows on the same query matrix with self_row NULL.
+ * ms (nullable) = HIP-event times summed over the passes: {query upload + GEMM, the deep selection}. Argument errors
+ * are reported before any device work: MSR_E_INVAL (a null dx / output, a null q with nq > 0, nq < 0, the precision
+ * mismatch), then MSR_E_RANGE (k). nq == 0 returns MSR_OK without a launch. The scratch stays with the handle and only
+ * grows (msr_dense_stats shows no allocation on a repeated call of one shape). */
+int msr_dense_search_deep(msr_dense* dx, const void* q, int q_is_f32, int nq, int k, uint32_t* out_idx,
+                          uint32_t* out_key, int32_t* out_n, float ms[2]);
 void msr_dense_close(msr_dense* dx);
 /* Bookkeeping of a dense handle: out = {hipMalloc calls made for its scratch so far, scratch bytes it holds, rows, dim}.
  * The scratch of msr_dense_search / msr_hybrid_search stays with the handle and is only ever grown, so repeated calls of

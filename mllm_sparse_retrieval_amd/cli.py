@@ -6,6 +6,7 @@
            --dataset_name flickr --queries out/query.tsv --qrels out/qrels.csv --save_dir runs/   (search_sparse.sh)
            [--ranks: exact rank of every judged doc at any depth -> recall / MRR / MedR / MeanR, sparse.ranks.tsv]
            [--explain N: per-token query weight x doc weight of the first N hits and the judged docs, sparse.explain.tsv]
+           [--deep: --depth up to 16384 (msr_search_deep; dense-only: msr_dense_search_deep; hybrid: with --host_fusion)]
     python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
            [--ranks: exact rank of every judged row at any depth (msr_dense_rank_rows) -> the same metrics, dense.ranks.tsv]
@@ -166,11 +167,22 @@ def normalize_rows(q):
 
 def _check_search_args(a):
     """Argument checks of `search` that need no index and no GPU."""
-    from ._cabi import MSR_KMAX
+    from ._cabi import MSR_DEEP_KMAX, MSR_KMAX
 
     if a.sparse_index is None and a.passage_reps is None:
         sys.exit("search: give --sparse_index (sparse or hybrid search) and/or --passage_reps (dense search)")
-    if a.sparse_index is None and not 1 <= a.depth <= MSR_KMAX:
+    deep = bool(getattr(a, "deep", False))
+    if deep:
+        if not 1 <= a.depth <= MSR_DEEP_KMAX:
+            sys.exit(f"search: --deep needs --depth in [1, MSR_DEEP_KMAX = {MSR_DEEP_KMAX}] (got {a.depth})")
+        if getattr(a, "fusion_union", False) or getattr(a, "hybrid_f32", False):
+            sys.exit("search: --deep does not combine with --fusion_union / --hybrid_f32: the fused GPU calls hold at most "
+                     f"MSR_KMAX = {MSR_KMAX} docs per list; deep hybrid search is --host_fusion --deep (two deep lists, "
+                     "fuse() on the host)")
+        if a.sparse_index is not None and a.passage_reps is not None and not a.host_fusion:
+            sys.exit("search: hybrid --deep needs --host_fusion (two deep lists per query and the reference's fuse() on the "
+                     f"host); the fused GPU route holds at most MSR_KMAX = {MSR_KMAX} docs per list")
+    if a.sparse_index is None and not deep and not 1 <= a.depth <= MSR_KMAX:
         sys.exit(f"search: dense-only --depth must be in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth})")
     if getattr(a, "ranks", False):
         if a.passage_reps is not None and a.sparse_index is not None:
@@ -268,7 +280,7 @@ def _cmd_search(a):
             qids = wanted
         texts = [""] * len(qids)
     else:
-        searcher = LuceneImpactSearcher(_index_path(a.sparse_index), None, device=a.device)
+        searcher = LuceneImpactSearcher(_index_path(a.sparse_index), None, device=a.device, deep=bool(getattr(a, "deep", False)))
         searcher.set_analyzer(JWhiteSpaceAnalyzer())
         qids, texts = read_queries(a.queries or os.path.join(a.sparse_index, "query.tsv"))
     n_queries = len(qids)
@@ -284,6 +296,7 @@ def _cmd_search(a):
     sparse_run, dense_run, fusion_run = {}, {}, {}
     args.batch_size, args.quiet = a.batch_size, True
     ds = dense_ranks = None
+    d_args = args  # what the dense side of --host_fusion searches with
     if dense_only and getattr(a, "ranks", False):  # the judged rows go through the same open index as the search
         ds = CrossModalQrels(a.qrels, a.dataset_name)
     t0 = time.time()
@@ -297,15 +310,19 @@ def _cmd_search(a):
         if p_reps is not None:  # --host_fusion: the reference's own structure, batch by batch (src/search.py:455-461)
             from .dense import FaissFlatSearcher
 
-            dense_retriever = FaissFlatSearcher(p_reps, device=a.device, precision="f32" if getattr(a, "hybrid_f32", False) else "fp16")
+            dense_retriever = FaissFlatSearcher(p_reps, device=a.device, precision="f32" if getattr(a, "hybrid_f32", False) else "fp16",
+                                                deep=bool(getattr(a, "deep", False)))
             dense_retriever.add(p_reps)
+            if getattr(a, "deep", False):  # a deep list never asks for more rows than the index holds
+                d_args = SimpleNamespace(**vars(args))
+                d_args.depth = min(a.depth, len(p_lookup))
         for i in range(0, len(qids), bs):
             scores, rankings = sparse_search(searcher, texts[i:i + bs], qids[i:i + bs], args)
             sparse_run.update(get_run_dict(qids[i:i + bs], scores, rankings, a.remove_query))
             if dense_retriever is not None:
                 q = np.stack([q_reps_by_id[x] for x in qids[i:i + bs]])
                 q = q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), 1e-12)    # F.normalize, src/search.py:342
-                d_scores, d_ids = search_queries(dense_retriever, q, p_lookup, args)
+                d_scores, d_ids = search_queries(dense_retriever, q, p_lookup, d_args)
                 dense_run.update(get_run_dict(qids[i:i + bs], d_scores, d_ids, a.remove_query))
         if dense_retriever is not None:
             from .fusion import fuse
@@ -467,6 +484,7 @@ def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids, ds=None):
     (no depth limit; --remove_query names the row whose id equals the query id as self_row), else None."""
     import numpy as np
 
+    from ._cabi import MSR_KMAX
     from .dense import DenseIndex, keys_to_f32
     from .run import get_run_dict
 
@@ -475,7 +493,11 @@ def _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids, ds=None):
     ranked = None
     dix = DenseIndex(p_reps, device=a.device, precision="fp16" if a.use_gpu else "f32")
     try:
-        d_scores, d_idx = dix.search(q, min(a.depth, dix.n))
+        depth = min(a.depth, dix.n)
+        if getattr(a, "deep", False) and depth > MSR_KMAX:
+            d_scores, d_idx = dix.search_deep(q, depth)
+        else:
+            d_scores, d_idx = dix.search(q, depth)
         if targets is not None:
             listing, t_ptr, t_row, self_row = targets
             ranks, keys = dix.rank_rows(q, t_ptr, t_row, self_row)
@@ -662,6 +684,12 @@ def main(argv=None):
                         "handle; --depth <= 1024, not with --host_fusion, --fusion_k is ignored")
     s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs (with or without --fusion_union; "
                                                                    "the fused run then feeds the recall report only: fusion.trec is written beside a dense run)")
+    s.add_argument("--deep", action="store_true",
+                   help="lists beyond 1024: lifts --depth to [1, MSR_DEEP_KMAX = 16384] on the sparse-only route "
+                        "(msr_search_deep), the dense-only route (msr_dense_search_deep; fp16 with --use_gpu, else f32) and, "
+                        "with --host_fusion, the hybrid route (two deep lists per query, fuse() on the host: fusion.trec "
+                        "holds the whole union); refused on the fused GPU hybrid routes, with --fusion_union and with "
+                        "--hybrid_f32; depths up to 1024 take the usual calls")
     s.add_argument("--ranks", action="store_true",
                    help="sparse search (--sparse_index alone) or dense search (--passage_reps alone, f32 or --use_gpu): after "
                         "the search, the EXACT rank (no depth limit) of every query's --qrels docs from one msr_rank_docs / "

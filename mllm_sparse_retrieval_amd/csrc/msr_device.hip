@@ -15,6 +15,7 @@
 #include "msr_rank.hpp"
 #include "msr_explain.hpp"
 #include "msr_doc_vectors.hpp"
+#include "msr_deep_select.hpp"
 
 namespace msr {
 
@@ -91,6 +92,24 @@ int launch_merge(hipStream_t st, const MergeArgs& a) {
         hipLaunchKernelGGL(merge_small, dim3((a.nq + 3) / 4), dim3(256), 0, st, a);  // one wave per query
     else
         hipLaunchKernelGGL((merge_lists<256>), dim3(a.nq), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return MSR_OK;
+}
+
+// deep_select_rows (msr_deep_select.hpp), one workgroup per row: the instance with the smallest composite buffer that
+// holds k keys (16 / 64 / 128 KiB of LDS + the histogram: 6 / 2 / 1 workgroups per CU).
+int launch_deep_select(hipStream_t st, const DeepArgs& a) {
+    if (a.rows == 0) return MSR_OK;
+    if (a.k < 1 || a.k > MSR_DEEP_KMAX || a.n > 0x7FFFFFFFu || a.rows > 0x7FFFFFFFu || a.ld % 4 != 0 || a.ld < a.n) {
+        set_error("deep_select_rows: k=%u, n=%u, ld=%llu, rows=%u outside its instances", a.k, a.n, (unsigned long long)a.ld, a.rows);
+        return MSR_E_RANGE;
+    }
+    if (a.k <= 2048)
+        hipLaunchKernelGGL((deep_select_rows<2048, 256>), dim3(a.rows), dim3(256), 0, st, a);
+    else if (a.k <= 8192)
+        hipLaunchKernelGGL((deep_select_rows<8192, 512>), dim3(a.rows), dim3(512), 0, st, a);
+    else
+        hipLaunchKernelGGL((deep_select_rows<MSR_DEEP_KMAX, 1024>), dim3(a.rows), dim3(1024), 0, st, a);
     HIP_TRY(hipGetLastError());
     return MSR_OK;
 }
@@ -1298,6 +1317,112 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
     if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
                !hip_ok(who, hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
         return MSR_E_HIP;
+    cs.ok = true;
+    return MSR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ deep lists
+// Score rows of one pass of msr_search_deep: at most this many bytes (the rule of the dense route, dense_passes: the rows
+// are read back by deep_select_rows out of the Infinity Cache).
+constexpr uint64_t kDeepPassBytes = 256ull << 20;
+
+int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int k,
+                    uint32_t flags, uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32, int32_t* out_n,
+                    float ms[2]) {
+    const char* const who = "msr_search_deep";
+    // ---- checks: shapes, then k, then the device
+    if (!ix || !q_ptr || nq < 0 || !out_doc_ord || !out_score || !out_n) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
+        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
+                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    if (k < 1 || k > MSR_DEEP_KMAX) {
+        set_error("%s: k must be in [1, MSR_DEEP_KMAX = %d] (got %d)", who, MSR_DEEP_KMAX, k);
+        return MSR_E_RANGE;
+    }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (nq == 0) return MSR_OK;
+    const IndexHeader* h = ix->host.h;
+    DeviceIndex* d = ix->dev;
+    const uint64_t ld = (uint64_t)h->n_tiles * h->tile_docs;
+    if (h->n_docs > 0x7FFFFFFFull) {
+        set_error("%s: %llu docs exceed the 2^31 - 1 columns of a score row", who, (unsigned long long)h->n_docs);
+        return MSR_E_RANGE;
+    }
+    // the queries, normalised and uploaded exactly as for a search (refusals included)
+    msr_batch* b = nullptr;
+    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
+    if (rc != MSR_OK) return rc;
+    CallScratch cs(d, b);
+    // ---- scratch of one pass: the score rows [qt][n_tiles * tile_docs] and the result rows [qt][k]
+    const uint32_t qt = (uint32_t)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, kDeepPassBytes / (ld * 4)));
+    const size_t s_bytes = (size_t)qt * ld * 4, r_bytes = (size_t)qt * k * 4;
+    uint32_t *d_S = cs.alloc(s_bytes), *d_idx = cs.alloc(r_bytes), *d_su = cs.alloc(r_bytes), *d_sf = cs.alloc(r_bytes),
+             *d_n = cs.alloc((size_t)qt * 4);
+    if (!d_S || !d_idx || !d_su || !d_sf || !d_n) {
+        set_error("%s: device allocation failed (%zu bytes of score rows, %u queries per pass)", who, s_bytes, qt);
+        return MSR_E_NOMEM;
+    }
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; ms && i < 3; ++i)
+        if (!(ev[i] = cs.event())) {
+            set_error("%s: hipEventCreate failed", who);
+            return MSR_E_HIP;
+        }
+    double t_score = 0, t_select = 0;
+    for (uint32_t q0 = 0; q0 < (uint32_t)nq; q0 += qt) {
+        const uint32_t qn = std::min<uint32_t>(qt, (uint32_t)nq - q0);
+        // the dump instance of score_tiles with one "rank" that owns every tile: row q - q0, column = doc ordinal
+        ScoreArgs sa;
+        fill_score_args(sa, b, 1);
+        sa.part = nullptr;
+        sa.q0 = q0;
+        sa.qn = qn;
+        sa.dump = d_S;
+        sa.tpr = h->n_tiles;
+        sa.dump_add = 0;
+        if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+        rc = launch_score(d->stream, h->tile_docs, 0, h->n_tiles, sa, true);
+        if (rc != MSR_OK) return rc;
+        if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+        DeepArgs da;
+        da.src = d_S;
+        da.ld = ld;
+        da.n = (uint32_t)h->n_docs;
+        da.rows = qn;
+        da.k = (uint32_t)k;
+        da.out_idx = d_idx;
+        da.out_key = d_su;
+        da.out_f32 = reinterpret_cast<float*>(d_sf);
+        da.out_n = reinterpret_cast<int32_t*>(d_n);
+        rc = launch_deep_select(d->stream, da);
+        if (rc != MSR_OK) return rc;
+        if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+        const size_t o = (size_t)q0 * k, nb = (size_t)qn * k * 4;
+        if (!hip_ok(who, hipStreamSynchronize(d->stream), "the scoring and selection kernels") ||
+            !hip_ok(who, hipMemcpy(out_doc_ord + o, d_idx, nb, hipMemcpyDeviceToHost), "download") ||
+            !hip_ok(who, hipMemcpy(out_score + o, d_sf, nb, hipMemcpyDeviceToHost), "download") ||
+            (out_score_u32 && !hip_ok(who, hipMemcpy(out_score_u32 + o, d_su, nb, hipMemcpyDeviceToHost), "download")) ||
+            !hip_ok(who, hipMemcpy(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost), "download"))
+            return MSR_E_HIP;
+        if (ms) {
+            float t0 = 0, t1 = 0;
+            if (!hip_ok(who, hipEventElapsedTime(&t0, ev[0], ev[1]), "hipEventElapsedTime") ||
+                !hip_ok(who, hipEventElapsedTime(&t1, ev[1], ev[2]), "hipEventElapsedTime"))
+                return MSR_E_HIP;
+            t_score += t0;
+            t_select += t1;
+        }
+    }
+    if (ms) ms[0] = (float)t_score, ms[1] = (float)t_select;
     cs.ok = true;
     return MSR_OK;
 }

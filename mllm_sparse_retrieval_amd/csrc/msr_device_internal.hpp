@@ -264,9 +264,23 @@ inline bool walk_route(bool has_table, bool light_batch, bool list_as_set, uint3
     return has_table && light_batch && !list_as_set && k <= kWalkMaxK && nq >= kWalkMinQueries;
 }
 
+// deep_select_rows (msr_deep_select.hpp): exact top-k, k <= MSR_DEEP_KMAX, of rows of u32 keys that sit in HBM
+struct DeepArgs {
+    const uint32_t* src;  // key(row, col) = src[row * ld + col], valid columns [0, n); key 0 = not a member
+    uint64_t ld;          // a multiple of 4, src 16-byte aligned
+    uint32_t n;
+    uint32_t rows;
+    uint32_t k;
+    uint32_t* out_idx;    // [rows][k] columns of the k best members by (key desc, col asc); 0xFFFFFFFF past out_n
+    uint32_t* out_key;    // [rows][k] their keys; 0 past out_n
+    float* out_f32;       // [rows][k] (float)key, or null
+    int32_t* out_n;       // [rows] min(k, members)
+};
+
 // defined in msr_device.hip
 int launch_select(hipStream_t st, uint32_t tile_docs, const SelectArgs& a);
 int launch_merge(hipStream_t st, const MergeArgs& a);
+int launch_deep_select(hipStream_t st, const DeepArgs& a);
 
 }  // namespace msr
 

@@ -133,7 +133,7 @@ struct msr_dense {
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
     // grown: six hipMalloc / hipFree pairs of up to 200 MB cost a call more than its kernels
     enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_USRC, S_USPARSE, S_UDENSE,
-                S_URANGE, S_RANK_IN, S_RANK_OUT, S_COUNT };
+                S_URANGE, S_RANK_IN, S_RANK_OUT, S_DEEP_IDX, S_DEEP_KEY, S_DEEP_N, S_COUNT };
     void* scratch[S_COUNT] = {};
     size_t scratch_bytes[S_COUNT] = {};
     uint64_t n_device_allocs = 0;  // hipMalloc calls made on behalf of this handle (steady-state calls make none)
@@ -595,6 +595,89 @@ int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, cons
         t_count += b;
     }
     if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_count;
+    return MSR_OK;
+}
+
+// Deep lists on the dense route: the passes and the GEMM of the search (dense_passes / dense_pass_scores), then
+// deep_select_rows (msr_deep_select.hpp, launched through msr_device.hip) over the pass's key rows in the place of
+// select_tiles + merge_lists, for k up to MSR_DEEP_KMAX.
+int msr_dense_search_deep(msr_dense* dx, const void* q, int q_is_f32, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
+                          int32_t* out_n, float ms[2]) {
+    const char* const who = "msr_dense_search_deep";
+    if (!dx || nq < 0 || (nq && !q) || !out_idx || !out_key || !out_n) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if ((q_is_f32 != 0) != dx->f32) {
+        if (dx->f32)
+            set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
+                      "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
+        else
+            set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
+                      "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
+        return MSR_E_INVAL;
+    }
+    if (k < 1 || k > MSR_DEEP_KMAX) {
+        set_error("%s: k must be in [1, MSR_DEEP_KMAX = %d] (got %d)", who, MSR_DEEP_KMAX, k);
+        return MSR_E_RANGE;
+    }
+    if (dx->device < 0) {
+        set_error("%s: the dense handle has no HIP device; there is no CPU dense search path", who);
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (nq == 0) return MSR_OK;
+    HIP_TRY(hipSetDevice(dx->device));
+    const DensePasses ps = dense_passes(dx, nq);
+    const uint32_t qt = ps.qt;
+    const size_t perq = (size_t)qt * k;
+    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
+    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
+    uint32_t* d_idx = (uint32_t*)dx->take(msr_dense::S_DEEP_IDX, perq * 4);
+    uint32_t* d_key = (uint32_t*)dx->take(msr_dense::S_DEEP_KEY, perq * 4);
+    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_DEEP_N, (size_t)qt * 4);
+    bool ok = d_Q && d_S && d_idx && d_key && d_n;
+    for (hipEvent_t& e : dx->ev)
+        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
+    if (!ok) {
+        set_error("device allocation failed in %s (%u queries per pass x %llu docs, k = %d)", who, qt, (unsigned long long)dx->n_pad, k);
+        return MSR_E_NOMEM;
+    }
+    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
+    double t_gemm = 0, t_sel = 0;
+    for (int q0 = 0; q0 < nq; q0 += (int)qt) {
+        const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
+        int rc = dense_pass_scores(dx, ps, q, q0, qn, d_Q, d_S, e0, true, who);
+        if (rc != MSR_OK) return rc;
+        (void)hipEventRecord(e1, dx->stream);
+        DeepArgs da;
+        da.src = d_S;
+        da.ld = dx->n_pad;
+        da.n = (uint32_t)dx->n;
+        da.rows = qn;
+        da.k = (uint32_t)k;
+        da.out_idx = d_idx;
+        da.out_key = d_key;
+        da.out_f32 = nullptr;
+        da.out_n = d_n;
+        rc = launch_deep_select(dx->stream, da);
+        if (rc != MSR_OK) return rc;
+        (void)hipEventRecord(e2, dx->stream);
+        const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_idx, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_key + (size_t)q0 * k, d_key, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipStreamSynchronize(dx->stream) == hipSuccess;
+        if (!c) {
+            set_error("%s: kernels or result download failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return MSR_E_HIP;
+        }
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, e0, e1);
+        (void)hipEventElapsedTime(&b, e1, e2);
+        t_gemm += a;
+        t_sel += b;
+    }
+    if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_sel;
     return MSR_OK;
 }
 

@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._cabi import check, lib, ptr
+from ._cabi import MSR_KMAX, check, lib, ptr
 
 
 def keys_to_f32(keys):
@@ -112,10 +112,36 @@ class DenseIndex:
         self.last_ms = (a.value, b.value)
         return idx, key, n
 
+    def search_keys_deep(self, q_reps, k):
+        """search_keys for 1 <= k <= MSR_DEEP_KMAX (msr_dense_search_deep): the same GEMM, the exact top-k of every key
+        row taken by the deep selection; bit-equal to search_keys for k <= MSR_KMAX."""
+        if self.precision == "f32":
+            q = _as_f32_rows(q_reps, self.dim)
+            q_ptr, is_f32 = ptr(q), 1
+        else:
+            q = _as_fp16_rows(q_reps, self.dim, self)   # (consumed by the synchronous call below)
+            q_ptr, is_f32 = ptr(q.view(np.uint16)), 0
+        nq = q.shape[0]
+        shape = (nq, max(int(k), 0))
+        idx = np.empty(shape, dtype=np.uint32)
+        key = np.empty(shape, dtype=np.uint32)
+        n = np.zeros(nq, dtype=np.int32)
+        ms = (C.c_float * 2)()
+        check(lib().msr_dense_search_deep(self._h, q_ptr, is_f32, nq, int(k), ptr(idx), ptr(key), ptr(n), ms))
+        self.last_ms = (ms[0], ms[1])
+        return idx, key, n
+
+    def search_deep(self, q_reps, k):
+        """search for 1 <= k <= MSR_DEEP_KMAX: (scores float32 [nq,k], indices int64 [nq,k]), (-inf, -1) past the hits."""
+        return self._scores_indices(*self.search_keys_deep(q_reps, k))
+
     def search(self, q_reps, k):
         """-> (scores float32 [nq,k], indices int64 [nq,k]); rows past the hit count hold (-inf, -1) like faiss."""
-        idx, key, n = self.search_keys(q_reps, k)
-        valid = np.arange(k)[None, :] < n[:, None]
+        return self._scores_indices(*self.search_keys(q_reps, k))
+
+    @staticmethod
+    def _scores_indices(idx, key, n):
+        valid = np.arange(idx.shape[1])[None, :] < n[:, None]
         scores = np.where(valid, keys_to_f32(key), -np.inf).astype(np.float32)
         indices = np.where(valid, idx.astype(np.int64), -1)
         return scores, indices
@@ -173,9 +199,10 @@ class FaissFlatSearcher:
     it to the GPU with useFloat16 (src/search.py:254-270). precision="f32" matches the CPU run (the k-ordered fmaf chain
     of f32 inputs, include/msr.h); the default "fp16" matches the --use_gpu run the hybrid script uses."""
 
-    def __init__(self, init_reps, device=0, precision="fp16"):
+    def __init__(self, init_reps, device=0, precision="fp16", deep=False):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        self.deep = bool(deep)  # k > MSR_KMAX goes through DenseIndex.search_deep (up to MSR_DEEP_KMAX)
         self._dim = np.asarray(init_reps).shape[1]
         self._parts = []
         self._index = None
@@ -199,15 +226,19 @@ class FaissFlatSearcher:
                                      precision=self.precision)
         return self._index
 
+    def _search(self, q_reps, k):
+        ix = self._ready()
+        return ix.search_deep(q_reps, k) if self.deep and k > MSR_KMAX else ix.search(q_reps, k)
+
     def search(self, q_reps, k):
-        return self._ready().search(q_reps, k)
+        return self._search(q_reps, k)
 
     def batch_search(self, q_reps, k, batch_size, quiet=False):
         q = np.asarray(q_reps)
-        ix = self._ready()
+        self._ready()
         scores, indices = [], []
         for i in range(0, q.shape[0], max(int(batch_size), 1)):
-            s, j = ix.search(q[i:i + batch_size], k)
+            s, j = self._search(q[i:i + batch_size], k)
             scores.append(s)
             indices.append(j)
         return np.concatenate(scores, axis=0), np.concatenate(indices, axis=0)

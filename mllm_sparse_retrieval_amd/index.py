@@ -201,6 +201,22 @@ class SparseIndex:
                                    ptr(su), ptr(n)))
         return ords, sc, su, n
 
+    def search_deep(self, q_ptr, q_term, q_w, k, drop_df_eq_n=True, with_ms=False):
+        """The ranked list for 1 <= k <= MSR_DEEP_KMAX (msr_search_deep): the outputs of search_csr, bit-equal to it for
+        k <= MSR_KMAX. with_ms=True appends the HIP-event times (scoring ms, deep selection ms)."""
+        q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
+        nq = len(q_ptr) - 1
+        shape = (nq, max(int(k), 0))
+        ords = np.empty(shape, dtype=np.uint32)
+        sc = np.empty(shape, dtype=np.float32)
+        su = np.empty(shape, dtype=np.uint32)
+        n = np.zeros(nq, dtype=np.int32)
+        ms = (C.c_float * 2)()
+        check(lib().msr_search_deep(self._h, ptr(q_ptr), ptr(q_term), ptr(q_w), nq, int(k),
+                                    MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(ords), ptr(sc), ptr(su), ptr(n),
+                                    C.cast(ms, C.c_void_p) if with_ms else None))
+        return (ords, sc, su, n, (float(ms[0]), float(ms[1]))) if with_ms else (ords, sc, su, n)
+
     def rank_docs(self, q_ptr, q_term, q_w, t_ptr, t_ord, drop_df_eq_n=True, self_ord=None, with_ms=False):
         """Exact ranks of listed docs (msr_rank_docs): query i lists the ordinals t_ord[t_ptr[i]:t_ptr[i + 1]] (at most
         MSR_RANK_MAX_TARGETS). Returns (ranks uint32, exact scores uint32), both indexed like t_ord: rank 0 = not a hit

@@ -60,13 +60,14 @@ class LuceneImpactSearcher:
                     docs in input order (a score tie goes to the doc indexed first, like Lucene's internal doc ids
                     under one indexing thread) instead of doc-id string order (contract T1, the default)."""
 
-    def __init__(self, index_dir, query_encoder=None, min_idf=0, device=0, drop_df_eq_n=None):
+    def __init__(self, index_dir, query_encoder=None, min_idf=0, device=0, drop_df_eq_n=None, deep=False):
         if query_encoder is not None:
             raise NotImplementedError("only query_encoder=None (token-frequency queries) is supported, as in the "
                                       "reference (src/search.py:273)")
         self.index = SparseIndex(index_dir, device=device)
         self.min_idf = min_idf
         self.drop_df_eq_n = drop_df_eq_n
+        self.deep = bool(deep)  # k > MSR_KMAX goes through SparseIndex.search_deep (up to MSR_DEEP_KMAX)
         self.num_docs = self.index.n_docs
 
     def set_analyzer(self, analyzer):
@@ -97,7 +98,15 @@ class LuceneImpactSearcher:
         if len(queries) != len(qids):
             raise ValueError("queries and qids differ in length")
         # a positive min_idf needs the term ids on this side (Python tokenisation), everything else tokenises in C
-        if self.min_idf > 0:
+        if self.deep and k > MSR_KMAX:
+            if self.min_idf > 0:
+                q_ptr, term_ids, ws = self._encode(queries)
+                ws, drop = self._idf_rule(term_ids, ws)
+            else:
+                q_ptr, term_ids, ws = self.index.encode_queries(queries)
+                drop = self._idf_rule(None, None)[1]
+            ords, scores, _, n = self.index.search_deep(q_ptr, term_ids, ws, k, drop_df_eq_n=drop)
+        elif self.min_idf > 0:
             q_ptr, term_ids, ws = self._encode(queries)
             ws, drop = self._idf_rule(term_ids, ws)
             ords, scores, _, n = self.index.search_csr(q_ptr, term_ids, ws, k, drop_df_eq_n=drop)

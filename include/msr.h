@@ -154,6 +154,37 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
                     uint32_t flags, uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32, int32_t* out_n,
                     float ms[2]);
 
+/* ---- filtered search: "search, but only among these docs". Every query names one of the call's doc SETS and its hits are
+ * the members of that set; Lucene does this with filter queries, which the reference never issues (its COCO 1K folds,
+ * one modality of a mixed corpus, a reranker's candidate list above the 64 listed docs of msr_rank_docs, tombstones:
+ * today each needs an index of its own).
+ * DOC SETS. set_bits is [n_sets][W] with W = (n + 31) / 32 words, n = n_docs here (on the dense route below: the number
+ * of rows, bits over ROW indices). Bit (o & 31) (bit 0 = LSB) of word (o >> 5) of row s says that doc o belongs to set
+ * s. Bits at or above n in the last word are ignored (they cannot surface a padding doc). q_set[i] in [-1, n_sets) picks
+ * the set of query i, -1 = the query is unfiltered. q_set may be NULL when n_sets is 0 (nothing is filtered) or 1 (every
+ * query uses set 0). At most MSR_FILTER_MAX_SETS sets per call.
+ * Queries are CSR and normalised exactly as by msr_search_csr (the same flags, the same MSR_E_OVERFLOW / MSR_E_RANGE
+ * refusals). The hits of query i are the docs of its set with score > 0; order (score descending, lower ordinal first),
+ * padding (0xFFFFFFFF / 0 / 0.f), the f32 image and out_n are those of msr_search_csr. 1 <= k <= MSR_KMAX. out_score_u32
+ * may be NULL. ms (nullable) = HIP-event times of {the scoring launches including the stage-1 merge, the final merge}.
+ * IDENTITIES: a full set, or q_set = -1, is bit-equal to msr_search_csr at that k; for any set the list equals the
+ * unfiltered exact ranking (msr_search_deep at a k that covers every hit) with the non-members struck out, cut to k; the
+ * lists of a set and of its complement partition the unfiltered hits.
+ * The scores are the search's own accumulation (accumulate_tile / accumulate_tile_light); a kernel of its own,
+ * score_tiles_filtered, masks the tile's scores with the set's bits before the unchanged selection, and a (tile, query)
+ * whose set holds no doc of the tile leaves before accumulating. The call always takes the staged launches of
+ * msr_batch_search: never the one-workgroup walk of small indexes and never the zero-copy path of small calls.
+ * Only a whole-index handle is served (doc-range and term-range shard handles: MSR_E_INVAL, as for msr_search_deep).
+ * Argument errors are reported before any device work, in this order: MSR_E_INVAL for a null ix / q_ptr / out_doc_ord /
+ * out_score / out_n, nq < 0, n_sets < 0, a null set_bits with n_sets > 0, a null q_set with n_sets > 1 and a shard
+ * handle; MSR_E_RANGE for k, for n_sets > MSR_FILTER_MAX_SETS and for a q_set entry outside [-1, n_sets); then
+ * MSR_E_NODEVICE on a handle opened with device < 0 (the CSR arrays themselves are checked with the normalisation).
+ * nq == 0 returns MSR_OK without a launch. Measured against the unfiltered search: DESIGN.md §5. */
+#define MSR_FILTER_MAX_SETS 65536 /* doc sets of one filtered call */
+int msr_search_filtered(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int k,
+                        uint32_t flags, const uint32_t* set_bits, int n_sets, const int32_t* q_set,
+                        uint32_t* out_doc_ord, float* out_score, uint32_t* out_score_u32, int32_t* out_n, float ms[2]);
+
 /* ---- exact ranks of listed docs: "where does this doc stand for this query", at any depth. Stands beside the ranked
  * lists the reference reads its hits from (src/search.py:86-99) and the recall counting over them (src/metrices.py);
  * there is NO counterpart call in the reference or in pyserini: a judged doc below the search depth is simply missing
@@ -390,6 +421,24 @@ int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, cons
  * grows (msr_dense_stats shows no allocation on a repeated call of one shape). */
 int msr_dense_search_deep(msr_dense* dx, const void* q, int q_is_f32, int nq, int k, uint32_t* out_idx,
                           uint32_t* out_key, int32_t* out_n, float ms[2]);
+/* Filtered search on the dense route: msr_dense_search / msr_dense_search_f32 among the rows of each query's set. The doc
+ * sets are those of msr_search_filtered with n = the number of rows and bits over ROW indices. q is [nq][h] in the handle's
+ * precision and q_is_f32 must match the handle (else MSR_E_INVAL), as in msr_dense_search_deep. Every row of the set is a
+ * hit (a flat index returns any score), so out_n[i] = min(k, |set|); order by key descending, ties to the lower ROW;
+ * outputs, key map and padding (0xFFFFFFFF / 0) are those of msr_dense_search; 1 <= k <= MSR_KMAX. The passes and the
+ * GEMM are the search's, so the same query matrix gives the same keys; select_tiles_filtered masks the keys on their way
+ * into LDS and the search's merge follows.
+ * IDENTITIES: a full set, or q_set = -1, is bit-equal to the search at that k on the same query matrix; for any set the
+ * list equals msr_dense_search_deep at a k that covers every row, with the non-members struck out, cut to k; a set and
+ * its complement partition the rows.
+ * ms (nullable) = HIP-event times summed over the passes: {query upload + GEMM, selection + merge}. Argument errors are
+ * reported before any device work, in this order: MSR_E_INVAL (a null dx / output, a null q with nq > 0, nq < 0,
+ * n_sets < 0, a null set_bits with n_sets > 0, a null q_set with n_sets > 1, the precision mismatch); MSR_E_RANGE (k,
+ * n_sets > MSR_FILTER_MAX_SETS, a q_set entry outside [-1, n_sets)); MSR_E_NODEVICE. nq == 0 returns MSR_OK without a
+ * launch. The scratch stays with the handle and only grows. */
+int msr_dense_search_filtered(msr_dense* dx, const void* q, int q_is_f32, int nq, int k, const uint32_t* set_bits,
+                              int n_sets, const int32_t* q_set, uint32_t* out_idx, uint32_t* out_key, int32_t* out_n,
+                              float ms[2]);
 void msr_dense_close(msr_dense* dx);
 /* Bookkeeping of a dense handle: out = {hipMalloc calls made for its scratch so far, scratch bytes it holds, rows, dim}.
  * The scratch of msr_dense_search / msr_hybrid_search stays with the handle and is only ever grown, so repeated calls of

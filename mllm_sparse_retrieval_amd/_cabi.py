@@ -17,6 +17,7 @@ MSR_F_DROP_DF_EQ_N = 1
 MSR_KMAX = 1024
 MSR_UNION_MAX = 2 * MSR_KMAX
 MSR_DEEP_KMAX = 16384
+MSR_FILTER_MAX_SETS = 65536
 MSR_RANK_MAX_TARGETS = 64
 MSR_EXPLAIN_MAX_TARGETS = 64
 MSR_DENSE_RANK_MAX_TARGETS = 64
@@ -64,6 +65,7 @@ SYMBOLS = [
     ("msr_docid_str", _I, [_VP, _U32, C.POINTER(_CP)]),
     ("msr_search_csr", _I, [_VP, _VP, _VP, _VP, _I, _I, _U32, _VP, _VP, _VP, _VP]),
     ("msr_search_deep", _I, [_VP, _VP, _VP, _VP, _I, _I, _U32, _VP, _VP, _VP, _VP, _VP]),
+    ("msr_search_filtered", _I, [_VP, _VP, _VP, _VP, _I, _I, _U32, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_rank_docs", _I, [_VP, _VP, _VP, _VP, _I, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_explain_docs", _I, [_VP, _VP, _VP, _VP, _I, _U32, _VP, _VP, _VP, C.c_int64, _VP]),
     ("msr_doc_vectors", _I, [_VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.POINTER(C.c_int64), _VP]),
@@ -101,6 +103,7 @@ SYMBOLS = [
     ("msr_dense_search_f32", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("msr_dense_rank_rows", _I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_dense_search_deep", _I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    ("msr_dense_search_filtered", _I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     ("msr_dense_close", None, [_VP]),
     ("msr_dense_stats", _I, [_VP, _VP]),
     ("msr_f32_to_f16", _I, [_VP, _VP, _U64, _I]),

@@ -204,6 +204,21 @@ def _check_search_args(a):
                      f"(got {a.explain})")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("search: --explain runs in one process (no launcher, WORLD_SIZE = 1)")
+    if getattr(a, "doc_sets", None) or getattr(a, "query_sets", None):
+        if not (a.doc_sets and a.query_sets):
+            sys.exit("search: filtered search needs both --doc_sets FILE (docid<TAB>set) and --query_sets FILE (qid<TAB>set)")
+        if deep or getattr(a, "ranks", False) or getattr(a, "explain", None) is not None:
+            sys.exit("search: --doc_sets / --query_sets do not combine with --deep, --ranks or --explain: filtered deep "
+                     "lists and filtered ranks are not served (filter a --deep run on the host instead)")
+        if a.sparse_index is not None and a.passage_reps is not None and not a.host_fusion:
+            sys.exit("search: filtered hybrid search needs --host_fusion (two filtered lists per query and the reference's "
+                     "fuse() on the host); the fused GPU hybrid calls take no doc sets")
+        if getattr(a, "fusion_union", False):
+            sys.exit("search: --doc_sets / --query_sets do not combine with --fusion_union (a fused GPU hybrid call)")
+        if not 1 <= a.depth <= MSR_KMAX:
+            sys.exit(f"search: filtered search needs --depth in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth})")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("search: --doc_sets / --query_sets run in one process (no launcher, WORLD_SIZE = 1)")
     if getattr(a, "hybrid_f32", False):
         if a.use_gpu:
             sys.exit("search: --hybrid_f32 and --use_gpu contradict each other (--use_gpu is the reference's fp16 GPU "
@@ -300,7 +315,10 @@ def _cmd_search(a):
     if dense_only and getattr(a, "ranks", False):  # the judged rows go through the same open index as the search
         ds = CrossModalQrels(a.qrels, a.dataset_name)
     t0 = time.time()
-    if dense_only:
+    filtered = bool(getattr(a, "doc_sets", None))
+    if filtered:  # sparse-only, dense-only or --host_fusion: one filtered call per side over the whole query file
+        sparse_run, dense_run, fusion_run = _filtered_search(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts)
+    elif dense_only:
         dense_run, dense_ranks = _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids, ds)
     elif p_reps is not None and not a.host_fusion:
         # Hybrid on the GPU (the default): this rank's WHOLE query shard in one msr_hybrid_search call — sparse scores,
@@ -380,6 +398,65 @@ def _cmd_search(a):
         searcher.close()
     if world > 1:
         dist.barrier()
+
+
+def _filtered_search(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
+    """search --doc_sets FILE --query_sets FILE: every query searches only the docs of its set (a query without a line
+    in --query_sets is unfiltered; a doc in no set belongs to no set). Sparse side: ONE batch_search_filtered call
+    (msr_search_filtered); dense side: ONE DenseIndex.search_filtered call (msr_dense_search_filtered) with the sets over
+    the rows of p_lookup, precision as on the unfiltered routes; with both (--host_fusion) the two filtered lists go
+    through the reference's fuse(). A doc id the searched index does not know is an error. Returns the three run dicts."""
+    import numpy as np
+
+    from .filters import read_doc_sets, read_query_sets
+    from .run import get_run_dict
+
+    doc_sets, query_set = read_doc_sets(a.doc_sets), read_query_sets(a.query_sets)
+    for qid in qids:
+        if qid in query_set and query_set[qid] not in doc_sets:
+            sys.exit(f"search: query {qid} names doc set {query_set[qid]!r}, which {a.doc_sets} does not define")
+    sparse_run, dense_run, fusion_run = {}, {}, {}
+    if searcher is not None:
+        try:
+            by_qid = searcher.batch_search_filtered(texts, qids, a.depth, doc_sets, query_set)
+        except ValueError as e:
+            sys.exit(f"search: {a.doc_sets}: {e}")
+        sparse_run = get_run_dict(qids, [[h.score for h in by_qid[x]] for x in qids],
+                                  [[h.docid for h in by_qid[x]] for x in qids], a.remove_query)
+    if p_reps is not None:
+        from .dense import DenseIndex
+
+        row_of = {}
+        for r, x in enumerate(p_lookup):
+            row_of.setdefault(str(x), []).append(r)
+        names = list(doc_sets)
+        member = np.zeros((len(names), len(p_lookup)), dtype=bool)
+        for s_i, name in enumerate(names):
+            for d in doc_sets[name]:
+                if str(d) not in row_of:
+                    sys.exit(f"search: {a.doc_sets}: doc set {name!r}: no dense row carries doc id {d!r}")
+                member[s_i, row_of[str(d)]] = True
+        col = {name: s_i for s_i, name in enumerate(names)}
+        q_set = np.asarray([col[query_set[x]] if x in query_set else -1 for x in qids], dtype=np.int32)
+        q = normalize_rows(np.stack([q_reps_by_id[x] for x in qids])) if qids else np.zeros((0, p_reps.shape[1]), np.float32)
+        if searcher is None:
+            precision = "fp16" if a.use_gpu else "f32"
+        else:
+            precision = "f32" if getattr(a, "hybrid_f32", False) else "fp16"
+        dix = DenseIndex(p_reps, device=a.device, precision=precision)
+        try:
+            d_scores, d_idx = dix.search_filtered(q, min(a.depth, dix.n), member, q_set)
+        finally:
+            dix.close()
+        lookup = [str(x) for x in p_lookup]
+        rows = [[j for j in d_idx[i].tolist() if j >= 0] for i in range(len(qids))]  # (a set smaller than the depth)
+        dense_run = get_run_dict(qids, [d_scores[i, :len(rows[i])] for i in range(len(qids))],   # (f32, as unfiltered)
+                                 [[lookup[j] for j in rows[i]] for i in range(len(qids))], a.remove_query)
+        if searcher is not None:
+            from .fusion import fuse
+
+            fusion_run = fuse([dense_run, sparse_run], [a.alpha, 1 - a.alpha])
+    return sparse_run, dense_run, fusion_run
 
 
 def _report_exact_ranks(a, searcher, ds, qids, texts):
@@ -690,6 +767,12 @@ def main(argv=None):
                         "with --host_fusion, the hybrid route (two deep lists per query, fuse() on the host: fusion.trec "
                         "holds the whole union); refused on the fused GPU hybrid routes, with --fusion_union and with "
                         "--hybrid_f32; depths up to 1024 take the usual calls")
+    s.add_argument("--doc_sets", default=None, metavar="FILE",
+                   help="filtered search: TSV lines docid<TAB>set naming doc sets; with --query_sets every query searches "
+                        "only the docs of its set (msr_search_filtered / msr_dense_search_filtered): sparse-only, dense-only "
+                        "and --host_fusion routes; refused on the GPU-fused hybrid routes and with --deep, --ranks, --explain")
+    s.add_argument("--query_sets", default=None, metavar="FILE",
+                   help="filtered search: TSV lines qid<TAB>set; a query without a line is unfiltered")
     s.add_argument("--ranks", action="store_true",
                    help="sparse search (--sparse_index alone) or dense search (--passage_reps alone, f32 or --use_gpu): after "
                         "the search, the EXACT rank (no depth limit) of every query's --qrels docs from one msr_rank_docs / "

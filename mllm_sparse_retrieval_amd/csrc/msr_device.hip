@@ -1427,6 +1427,119 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
     return MSR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ filtered search
+// The staged path of batch_search_local restated for score_tiles_filtered: stage 1 over max(1, nt / kStage1Fraction) tiles
+// when the launch is big enough, its merge, the rest of the tiles with the thresholds, the final merge. A masked score is
+// 0, so a threshold of stage 1 is a bound among the MEMBERS of the query's set and stays exact. The call never takes
+// score_tiles_walk and never the zero-copy block of small calls (its batch is an ordinary pooled one).
+int msr_search_filtered(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int k,
+                        uint32_t flags, const uint32_t* set_bits, int n_sets, const int32_t* q_set, uint32_t* out_doc_ord,
+                        float* out_score, uint32_t* out_score_u32, int32_t* out_n, float ms[2]) {
+    const char* const who = "msr_search_filtered";
+    // ---- checks: shapes, then ranges, then the device
+    if (!ix || !q_ptr || nq < 0 || !out_doc_ord || !out_score || !out_n) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if (int rc0 = filter_check_shapes(who, set_bits, n_sets, q_set)) return rc0;
+    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
+        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
+                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    if (k < 1 || k > MSR_KMAX) {
+        set_error("%s: k must be in [1, MSR_KMAX = %d] (got %d)", who, MSR_KMAX, k);
+        return MSR_E_RANGE;
+    }
+    if (int rc0 = filter_check_ranges(who, n_sets, q_set, nq)) return rc0;
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (nq == 0) return MSR_OK;
+    const IndexHeader* h = ix->host.h;
+    DeviceIndex* d = ix->dev;
+    if ((uint64_t)h->n_tiles * h->tile_docs > 0xFFFFFFFFull) {
+        set_error("%s: %llu docs exceed the 2^32 bits of a doc-set row", who, (unsigned long long)h->n_docs);
+        return MSR_E_RANGE;
+    }
+    // the queries, normalised and uploaded exactly as for a search (refusals included); result buffers for k
+    msr_batch* b = nullptr;
+    int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, k, flags, 0, 0, &b);
+    if (rc != MSR_OK) return rc;
+    CallScratch cs(d, b);
+    // ---- the doc sets: bitmap | any | q_set, one block
+    FilterImage fi;
+    fi.build(set_bits, n_sets, q_set, nq, h->n_docs, h->tile_docs, h->n_tiles);
+    const size_t o_bits = cs.put(fi.bits), o_any = cs.put(fi.any), o_qs = cs.put(fi.q_set);
+    const size_t in_bytes = cs.in.size() * 4;
+    uint32_t* d_in = cs.alloc(in_bytes);
+    if (!d_in) {
+        set_error("%s: device allocation failed (%zu bytes of doc sets)", who, in_bytes);
+        return MSR_E_NOMEM;
+    }
+    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the doc sets")) return MSR_E_HIP;
+    FilterArgs fa;
+    fa.bits = d_in + o_bits;
+    fa.any = reinterpret_cast<const uint8_t*>(d_in + o_any);
+    fa.q_set = reinterpret_cast<const int32_t*>(d_in + o_qs);
+    fa.stride = fi.stride;
+    fa.n_tiles = h->n_tiles;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; ms && i < 3; ++i)
+        if (!(ev[i] = cs.event())) {
+            set_error("%s: hipEventCreate failed", who);
+            return MSR_E_HIP;
+        }
+    // ---- launches
+    ScoreArgs sa;
+    fill_score_args(sa, b, k);
+    sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;
+    const uint32_t nt = ix->shard_ntiles;
+    uint32_t t1 = nt;
+    if (nt >= 2 && (uint64_t)nt * (uint64_t)nq >= kMinStagedPairs) t1 = std::max<uint32_t>(1u, nt / kStage1Fraction);
+    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    rc = launch_score_filtered(d->stream, h->tile_docs, 0, t1, sa, fa);
+    if (rc != MSR_OK) return rc;
+    MergeArgs ma;
+    ma.lists = b->d_part;
+    ma.list_stride = (uint64_t)nq * k;
+    ma.nq = (uint32_t)nq;
+    ma.k = (uint32_t)k;
+    ma.out_keys = b->d_keys;
+    if (t1 < nt) {
+        ma.n_lists = t1;
+        ma.out_ord = nullptr;
+        ma.out_score_u32 = nullptr;
+        ma.out_score = nullptr;
+        ma.out_n = nullptr;
+        rc = launch_merge(d->stream, ma);
+        if (rc != MSR_OK) return rc;
+        sa.theta = b->d_keys;
+        rc = launch_score_filtered(d->stream, h->tile_docs, t1, nt, sa, fa);
+        if (rc != MSR_OK) return rc;
+    }
+    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    ma.n_lists = nt;
+    ma.out_ord = b->d_ord;
+    ma.out_score_u32 = b->d_su32;
+    ma.out_score = b->d_sf32;
+    ma.out_n = b->d_n;
+    rc = launch_merge(d->stream, ma);
+    if (rc != MSR_OK) return rc;
+    if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    // ---- download (msr_batch_fetch waits for the stream)
+    b->last_k = k;
+    rc = msr_batch_fetch(b, out_doc_ord, out_score, out_score_u32, out_n);
+    if (rc != MSR_OK) return rc;
+    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
+               !hip_ok(who, hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
+        return MSR_E_HIP;
+    cs.ok = true;
+    return MSR_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ explain listed docs
 int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq,
                      uint32_t flags, const int64_t* t_ptr, const uint32_t* t_ord, uint32_t* out_doc_w, int64_t out_cap,

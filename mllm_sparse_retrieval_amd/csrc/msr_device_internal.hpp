@@ -1,4 +1,4 @@
-// Shared by the two HIP translation units (msr_device.hip, msr_hybrid.hip): device-side state of an index, kernel
+// Shared by the HIP translation units (msr_device.hip, msr_hybrid.hip, msr_filter.hip): device-side state of an index, kernel
 // argument blocks, the resident query batch, and the few host functions that cross the unit boundary.
 #pragma once
 
@@ -277,10 +277,78 @@ struct DeepArgs {
     int32_t* out_n;       // [rows] min(k, members)
 };
 
+// Filtered search (msr_filter.hpp): the doc sets of one call as the kernels read them.
+struct FilterArgs {
+    const uint32_t* bits;  // [n_sets][stride]: bit (o & 31) of word (o >> 5) of row s = doc / row o belongs to set s
+    const uint8_t* any;    // [n_sets][n_tiles]: does set s hold a doc of tile t
+    const int32_t* q_set;  // [nq of the call]: the set of each query, -1 = unfiltered
+    uint32_t stride;       // words per bitmap row = n_tiles * tile_docs / 32 (zero padded: a ragged last tile reads in bounds)
+    uint32_t n_tiles;      // tiles of the whole index
+};
+
+// The host image of a call's doc sets, shared by msr_search_filtered and msr_dense_search_filtered. `set_bits` is the
+// caller's [n_sets][(n + 31) / 32] bitmap over n docs / rows, `q_set` its per-query choice (may be null: no set -> every
+// query unfiltered, one set -> every query uses it). One pass copies every row into the device layout (row stride
+// n_tiles * tile_docs / 32 words, zero padded), clears the bits at or above n and fills any[set][tile].
+struct FilterImage {
+    std::vector<uint32_t> bits;   // [n_sets][stride]
+    std::vector<uint32_t> any;    // n_sets * n_tiles bytes, packed into words for the upload
+    std::vector<uint32_t> q_set;  // [nq] (int32 values)
+    uint32_t stride = 0;
+    void build(const uint32_t* set_bits, int n_sets, const int32_t* q_set_in, int nq, uint64_t n, uint32_t tile_docs,
+               uint32_t n_tiles) {
+        const uint64_t w_in = (n + 31) / 32;
+        const uint32_t tile_words = tile_docs / 32;
+        stride = n_tiles * tile_words;
+        bits.assign(std::max<size_t>((size_t)n_sets * stride, 1), 0u);
+        any.assign(((size_t)n_sets * n_tiles + 3) / 4 + 1, 0u);
+        uint8_t* const any8 = reinterpret_cast<uint8_t*>(any.data());
+        for (int s = 0; s < n_sets; ++s) {
+            uint32_t* row = bits.data() + (size_t)s * stride;
+            if (w_in) memcpy(row, set_bits + (size_t)s * w_in, (size_t)w_in * 4);
+            if (n % 32) row[w_in - 1] &= (1u << (n % 32)) - 1u;  // bits at or above n cannot surface a padding doc
+            for (uint32_t t = 0; t < n_tiles; ++t) {
+                uint32_t acc = 0;
+                for (uint32_t w = 0; w < tile_words; ++w) acc |= row[(size_t)t * tile_words + w];
+                any8[(size_t)s * n_tiles + t] = acc != 0;
+            }
+        }
+        q_set.resize(std::max(nq, 1));
+        for (int i = 0; i < nq; ++i) q_set[i] = (uint32_t)(q_set_in ? q_set_in[i] : (n_sets == 0 ? -1 : 0));
+    }
+};
+
+// The argument checks of the two filtered calls that concern the sets. Shapes (MSR_E_INVAL) ...
+inline int filter_check_shapes(const char* who, const uint32_t* set_bits, int n_sets, const int32_t* q_set) {
+    if (n_sets < 0 || (n_sets > 0 && !set_bits) || (n_sets > 1 && !q_set)) {
+        set_error("%s: bad doc sets (n_sets = %d%s%s)", who, n_sets, n_sets > 0 && !set_bits ? ", null set_bits" : "",
+                  n_sets > 1 && !q_set ? ", null q_set with more than one set" : "");
+        return MSR_E_INVAL;
+    }
+    return MSR_OK;
+}
+// ... and ranges (MSR_E_RANGE).
+inline int filter_check_ranges(const char* who, int n_sets, const int32_t* q_set, int nq) {
+    if (n_sets > MSR_FILTER_MAX_SETS) {
+        set_error("%s: %d doc sets, at most MSR_FILTER_MAX_SETS = %d", who, n_sets, MSR_FILTER_MAX_SETS);
+        return MSR_E_RANGE;
+    }
+    for (int i = 0; q_set && i < nq; ++i)
+        if (q_set[i] < -1 || q_set[i] >= n_sets) {
+            set_error("%s: q_set[%d] = %d is outside [-1, n_sets = %d)", who, i, q_set[i], n_sets);
+            return MSR_E_RANGE;
+        }
+    return MSR_OK;
+}
+
 // defined in msr_device.hip
 int launch_select(hipStream_t st, uint32_t tile_docs, const SelectArgs& a);
 int launch_merge(hipStream_t st, const MergeArgs& a);
 int launch_deep_select(hipStream_t st, const DeepArgs& a);
+// defined in msr_filter.hip
+int launch_score_filtered(hipStream_t st, uint32_t tile_docs, uint32_t t_begin, uint32_t t_end, const ScoreArgs& a0,
+                          const FilterArgs& f);
+int launch_select_filtered(hipStream_t st, uint32_t tile_docs, const SelectArgs& a, const FilterArgs& f);
 
 }  // namespace msr
 

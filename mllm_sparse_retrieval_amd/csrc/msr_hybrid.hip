@@ -133,7 +133,7 @@ struct msr_dense {
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
     // grown: six hipMalloc / hipFree pairs of up to 200 MB cost a call more than its kernels
     enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_USRC, S_USPARSE, S_UDENSE,
-                S_URANGE, S_RANK_IN, S_RANK_OUT, S_DEEP_IDX, S_DEEP_KEY, S_DEEP_N, S_COUNT };
+                S_URANGE, S_RANK_IN, S_RANK_OUT, S_DEEP_IDX, S_DEEP_KEY, S_DEEP_N, S_FILTER, S_COUNT };
     void* scratch[S_COUNT] = {};
     size_t scratch_bytes[S_COUNT] = {};
     uint64_t n_device_allocs = 0;  // hipMalloc calls made on behalf of this handle (steady-state calls make none)
@@ -665,6 +665,128 @@ int msr_dense_search_deep(msr_dense* dx, const void* q, int q_is_f32, int nq, in
         (void)hipEventRecord(e2, dx->stream);
         const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_idx, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
                        hipMemcpyAsync(out_key + (size_t)q0 * k, d_key, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipStreamSynchronize(dx->stream) == hipSuccess;
+        if (!c) {
+            set_error("%s: kernels or result download failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return MSR_E_HIP;
+        }
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, e0, e1);
+        (void)hipEventElapsedTime(&b, e1, e2);
+        t_gemm += a;
+        t_sel += b;
+    }
+    if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_sel;
+    return MSR_OK;
+}
+
+// Filtered search on the dense route: the passes and the GEMM of the search (dense_passes / dense_pass_scores), then
+// select_tiles_filtered (msr_filter.hpp, launched through msr_filter.hip) in the place of select_tiles, then the search's
+// merge. The doc sets are uploaded once per call (S_FILTER: bitmap | any | q_set); the kernel indexes q_set by the call's
+// query, the per-tile lists are pass-local.
+int msr_dense_search_filtered(msr_dense* dx, const void* q, int q_is_f32, int nq, int k, const uint32_t* set_bits,
+                              int n_sets, const int32_t* q_set, uint32_t* out_idx, uint32_t* out_key, int32_t* out_n,
+                              float ms[2]) {
+    const char* const who = "msr_dense_search_filtered";
+    if (!dx || nq < 0 || (nq && !q) || !out_idx || !out_key || !out_n) {
+        set_error("%s: bad argument", who);
+        return MSR_E_INVAL;
+    }
+    if (int rc0 = filter_check_shapes(who, set_bits, n_sets, q_set)) return rc0;
+    if ((q_is_f32 != 0) != dx->f32) {
+        if (dx->f32)
+            set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
+                      "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
+        else
+            set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
+                      "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
+        return MSR_E_INVAL;
+    }
+    if (k < 1 || k > MSR_KMAX) {
+        set_error("%s: k must be in [1, MSR_KMAX = %d] (got %d)", who, MSR_KMAX, k);
+        return MSR_E_RANGE;
+    }
+    if (int rc0 = filter_check_ranges(who, n_sets, q_set, nq)) return rc0;
+    if (dx->device < 0) {
+        set_error("%s: the dense handle has no HIP device; there is no CPU dense search path", who);
+        return MSR_E_NODEVICE;
+    }
+    if (ms) ms[0] = ms[1] = 0.f;
+    if (nq == 0) return MSR_OK;
+    HIP_TRY(hipSetDevice(dx->device));
+    const DensePasses ps = dense_passes(dx, nq);
+    const uint32_t qt = ps.qt;
+    const size_t perq = (size_t)qt * k;
+    FilterImage fi;
+    fi.build(set_bits, n_sets, q_set, nq, dx->n, dx->tile_docs, dx->n_tiles);
+    auto al = [](size_t n) { return (n + 63) / 64 * 64; };  // sub-buffers start on 256-byte boundaries (in u32 units)
+    const size_t o_bits = 0, o_any = al(fi.bits.size()), o_qs = o_any + al(fi.any.size()), f_words = o_qs + al(fi.q_set.size());
+    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
+    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
+    uint64_t* d_part = (uint64_t*)dx->take(msr_dense::S_PART, (size_t)dx->n_tiles * perq * 8);
+    uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perq * 4);
+    uint32_t* d_su = (uint32_t*)dx->take(msr_dense::S_SU, perq * 4);
+    float* d_sf = (float*)dx->take(msr_dense::S_SF, perq * 4);
+    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_N, (size_t)qt * 4);
+    uint32_t* d_f = (uint32_t*)dx->take(msr_dense::S_FILTER, f_words * 4);
+    bool ok = d_Q && d_S && d_part && d_ord && d_su && d_sf && d_n && d_f;
+    for (hipEvent_t& e : dx->ev)
+        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
+    if (!ok) {
+        set_error("device allocation failed in %s (%u queries per pass x %llu docs, %d sets)", who, qt,
+                  (unsigned long long)dx->n_pad, n_sets);
+        return MSR_E_NOMEM;
+    }
+    if (hipMemcpy(d_f + o_bits, fi.bits.data(), fi.bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_f + o_any, fi.any.data(), fi.any.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_f + o_qs, fi.q_set.data(), fi.q_set.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: upload of the doc sets failed", who);
+        return MSR_E_HIP;
+    }
+    FilterArgs fa;
+    fa.bits = d_f + o_bits;
+    fa.any = reinterpret_cast<const uint8_t*>(d_f + o_any);
+    fa.q_set = reinterpret_cast<const int32_t*>(d_f + o_qs);
+    fa.stride = fi.stride;
+    fa.n_tiles = dx->n_tiles;
+    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
+    double t_gemm = 0, t_sel = 0;
+    for (int q0 = 0; q0 < nq; q0 += (int)qt) {
+        const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
+        int rc = dense_pass_scores(dx, ps, q, q0, qn, d_Q, d_S, e0, true, who);
+        if (rc != MSR_OK) return rc;
+        (void)hipEventRecord(e1, dx->stream);
+        SelectArgs se;
+        se.src = d_S;
+        se.part = d_part;
+        se.n_docs = dx->n;
+        se.n_tiles = dx->n_tiles;
+        se.tpr = dx->n_tiles;
+        se.rank = 0;
+        se.nq = qn;
+        se.q0 = (uint32_t)q0;  // the pass's first query in the call: q_set is indexed by q0 + qi, `part` by qi
+        se.qn = qn;
+        se.k = (uint32_t)k;
+        se.unsorted = 0;
+        rc = launch_select_filtered(dx->stream, dx->tile_docs, se, fa);
+        if (rc != MSR_OK) return rc;
+        MergeArgs ma;
+        ma.lists = d_part;
+        ma.list_stride = (uint64_t)qn * k;
+        ma.n_lists = dx->n_tiles;
+        ma.nq = qn;
+        ma.k = (uint32_t)k;
+        ma.out_keys = nullptr;
+        ma.out_ord = d_ord;
+        ma.out_score_u32 = d_su;
+        ma.out_score = d_sf;
+        ma.out_n = d_n;
+        rc = launch_merge(dx->stream, ma);
+        if (rc != MSR_OK) return rc;
+        (void)hipEventRecord(e2, dx->stream);
+        const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_ord, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                       hipMemcpyAsync(out_key + (size_t)q0 * k, d_su, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
                        hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
                        hipStreamSynchronize(dx->stream) == hipSuccess;
         if (!c) {

@@ -135,6 +135,36 @@ class DenseIndex:
         """search for 1 <= k <= MSR_DEEP_KMAX: (scores float32 [nq,k], indices int64 [nq,k]), (-inf, -1) past the hits."""
         return self._scores_indices(*self.search_keys_deep(q_reps, k))
 
+    def search_keys_filtered(self, q_reps, k, sets, q_set=None):
+        """search_keys among the rows of each query's set (msr_dense_search_filtered). `sets`: bool [n_sets, n] or packed
+        uint32 [n_sets, (n + 31) // 32] over ROW indices; q_set[i] in [-1, n_sets), -1 = unfiltered (None: no set, or one
+        set for every query). Every row of the set is a hit: the hit count is min(k, |set|)."""
+        from .filters import as_packed_sets, as_q_set
+
+        if self.precision == "f32":
+            q = _as_f32_rows(q_reps, self.dim)
+            q_ptr, is_f32 = ptr(q), 1
+        else:
+            q = _as_fp16_rows(q_reps, self.dim, self)   # (consumed by the synchronous call below)
+            q_ptr, is_f32 = ptr(q.view(np.uint16)), 0
+        nq = q.shape[0]
+        bits = as_packed_sets(sets, self.n)
+        qs = as_q_set(q_set, nq, bits.shape[0])
+        shape = (nq, max(int(k), 0))
+        idx = np.empty(shape, dtype=np.uint32)
+        key = np.empty(shape, dtype=np.uint32)
+        n = np.zeros(nq, dtype=np.int32)
+        ms = (C.c_float * 2)()
+        check(lib().msr_dense_search_filtered(self._h, q_ptr, is_f32, nq, int(k), ptr(bits) if bits.shape[0] else None,
+                                              int(bits.shape[0]), ptr(qs), ptr(idx), ptr(key), ptr(n), ms))
+        self.last_ms = (ms[0], ms[1])
+        return idx, key, n
+
+    def search_filtered(self, q_reps, k, sets, q_set=None):
+        """search among the rows of each query's set: (scores float32 [nq,k], indices int64 [nq,k]), (-inf, -1) past the
+        hits (a set smaller than k)."""
+        return self._scores_indices(*self.search_keys_filtered(q_reps, k, sets, q_set))
+
     def search(self, q_reps, k):
         """-> (scores float32 [nq,k], indices int64 [nq,k]); rows past the hit count hold (-inf, -1) like faiss."""
         return self._scores_indices(*self.search_keys(q_reps, k))
@@ -232,6 +262,10 @@ class FaissFlatSearcher:
 
     def search(self, q_reps, k):
         return self._search(q_reps, k)
+
+    def search_filtered(self, q_reps, k, sets, q_set=None):
+        """search among the rows of each query's set (DenseIndex.search_filtered): sets over ROW indices in add() order."""
+        return self._ready().search_filtered(q_reps, k, sets, q_set)
 
     def batch_search(self, q_reps, k, batch_size, quiet=False):
         q = np.asarray(q_reps)

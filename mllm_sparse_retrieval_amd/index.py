@@ -217,6 +217,29 @@ class SparseIndex:
                                     C.cast(ms, C.c_void_p) if with_ms else None))
         return (ords, sc, su, n, (float(ms[0]), float(ms[1]))) if with_ms else (ords, sc, su, n)
 
+    def search_filtered(self, q_ptr, q_term, q_w, k, sets, q_set=None, drop_df_eq_n=True, with_ms=False):
+        """search_csr among the docs of each query's set (msr_search_filtered). `sets`: bool [n_sets, n_docs] or packed
+        uint32 [n_sets, (n_docs + 31) // 32] (filters.pack_doc_sets); q_set[i] in [-1, n_sets) picks the set of query i,
+        -1 = unfiltered; q_set=None is allowed for no set (nothing filtered) or one set (every query uses it). The
+        outputs are those of search_csr; with_ms=True appends the HIP-event times (scoring ms, final merge ms)."""
+        from .filters import as_packed_sets, as_q_set
+
+        q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
+        nq = len(q_ptr) - 1
+        bits = as_packed_sets(sets, self.n_docs)
+        qs = as_q_set(q_set, nq, bits.shape[0])
+        shape = (nq, max(int(k), 0))
+        ords = np.empty(shape, dtype=np.uint32)
+        sc = np.empty(shape, dtype=np.float32)
+        su = np.empty(shape, dtype=np.uint32)
+        n = np.zeros(nq, dtype=np.int32)
+        ms = (C.c_float * 2)()
+        check(lib().msr_search_filtered(self._h, ptr(q_ptr), ptr(q_term), ptr(q_w), nq, int(k),
+                                        MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(bits) if bits.shape[0] else None,
+                                        int(bits.shape[0]), ptr(qs), ptr(ords), ptr(sc), ptr(su), ptr(n),
+                                        C.cast(ms, C.c_void_p) if with_ms else None))
+        return (ords, sc, su, n, (float(ms[0]), float(ms[1]))) if with_ms else (ords, sc, su, n)
+
     def rank_docs(self, q_ptr, q_term, q_w, t_ptr, t_ord, drop_df_eq_n=True, self_ord=None, with_ms=False):
         """Exact ranks of listed docs (msr_rank_docs): query i lists the ordinals t_ord[t_ptr[i]:t_ptr[i + 1]] (at most
         MSR_RANK_MAX_TARGETS). Returns (ranks uint32, exact scores uint32), both indexed like t_ord: rank 0 = not a hit

@@ -122,6 +122,53 @@ class LuceneImpactSearcher:
             out[qid] = [Hit(ids[j], row[j]) for j in range(cnt)]
         return out
 
+    def batch_search_filtered(self, queries, qids, k, doc_sets, query_set):
+        """batch_search among named doc sets (SparseIndex.search_filtered): doc_sets maps a set name to external doc ids,
+        query_set maps a qid to the name of its set; a qid without an entry is unfiltered. Returns {qid: [Hit, ...]} like
+        batch_search (duplicate qids collapse). A doc id the index does not hold, or a set name doc_sets does not have,
+        is a ValueError; a doc that is listed in no set belongs to no set. Counterpart: a Lucene filter query, which
+        pyserini's batch_search does not take."""
+        from .filters import sets_from_ordinals
+
+        if len(queries) != len(qids):
+            raise ValueError("queries and qids differ in length")
+        if getattr(self, "_ord_of", None) is None:
+            self._ord_of = {d: o for o, d in enumerate(self.index.docid_table().tolist())}
+        ord_of = self._ord_of
+        names = list(doc_sets)
+        col = {name: s for s, name in enumerate(names)}
+        lists = []
+        for name in names:
+            unknown = [str(d) for d in doc_sets[name] if str(d) not in ord_of]
+            if unknown:
+                raise ValueError(f"doc set {name!r}: the index does not hold doc id {unknown[0]!r}"
+                                 + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+            lists.append([ord_of[str(d)] for d in doc_sets[name]])
+        q_set = np.full(len(qids), -1, dtype=np.int32)
+        for i, qid in enumerate(qids):
+            name = query_set.get(qid)
+            if name is None:
+                continue
+            if name not in col:
+                raise ValueError(f"query {qid!r} names doc set {name!r}, which doc_sets does not have")
+            q_set[i] = col[name]
+        if self.min_idf > 0:
+            q_ptr, term_ids, ws = self._encode(queries)
+        else:
+            q_ptr, term_ids, ws = self.index.encode_queries(queries)
+        ws, drop = self._idf_rule(term_ids, ws)
+        bits = sets_from_ordinals(lists, self.index.n_docs)
+        ords, scores, _, n = self.index.search_filtered(q_ptr, term_ids, ws, k, bits, q_set, drop_df_eq_n=drop)
+        out = {}
+        table = self.index.docid_table()
+        score_rows = scores.tolist()
+        for i, qid in enumerate(qids):
+            cnt = int(n[i])
+            ids = table[ords[i, :cnt]].tolist()
+            row = score_rows[i]
+            out[qid] = [Hit(ids[j], row[j]) for j in range(cnt)]
+        return out
+
     def batch_rank(self, queries, qids, targets, remove_query=False):
         """Exact rank and score of named docs: targets[i] lists external doc ids for queries[i]. Returns
         {qid: [(docid, rank, score), ...]} in the given order; rank 0 = not a hit (score 0) or, with remove_query, the

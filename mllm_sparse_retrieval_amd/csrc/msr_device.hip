@@ -571,10 +571,7 @@ static int batch_create_impl(msr_index* ix, const int64_t* q_ptr, const int32_t*
         set_error("msr_batch_create: bad argument");
         return MSR_E_INVAL;
     }
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
-        return MSR_E_NODEVICE;
-    }
+    if (int rc0 = device_check(ix)) return rc0;
     if (kmax < 1 || kmax > MSR_KMAX) {
         set_error("k must be in [1, %d] (got %d)", MSR_KMAX, kmax);
         return MSR_E_RANGE;
@@ -881,85 +878,55 @@ int msr_batch_create_termshard(msr_index* ix, const int64_t* q_ptr, const int32_
     return batch_create_impl(ix, q_ptr, q_term, q_w, nq, kmax, flags, shard, n_shards, out);
 }
 
-int batch_search_local(msr_batch* b, int k, bool final_arrays) {
-    msr_index* ix = b->ix;
-    DeviceIndex* d = ix->dev;
-    const IndexHeader* h = ix->host.h;
-    HIP_TRY(hipSetDevice(d->device));
-    if (!b->untimed)
-        if (int rc0 = batch_begin_timed(b)) return rc0;
-    ScoreArgs sa;
+// fill_score_args plus the two fields that only a search sets
+static void fill_search_args(ScoreArgs& sa, msr_batch* b, int k) {
     fill_score_args(sa, b, k);
     sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;
-    // Staged search: the first `t1` tiles are scored with the full per-tile selection; their merged k-th best key
-    // per query is a lower bound on the final k-th key, so the remaining tiles only have to report keys at or above
-    // it (theta_select: one pass, usually no survivor). Exact: the final merge sees every key that can be in the
-    // top-k. (A launch holds at most 65535 tiles in y; x = queries.)
-    int rc = MSR_OK;
-    const uint32_t nt = ix->shard_ntiles;
-    if (walk_route(d->d_walk != nullptr, sa.light != 0, b->unsorted_ok, (uint32_t)b->nq, (uint32_t)k)) {
-        // small index, many light queries: one workgroup per query walks the tiles and writes the result rows itself
-        // (msr_walk.hpp): no per-tile lists, no merge launch. The whole kernel counts as score time.
-        WalkArgs wa;
-        wa.s = sa;
-        wa.m.lists = nullptr;
-        wa.m.list_stride = 0;
-        wa.m.n_lists = 0;
-        wa.m.nq = (uint32_t)b->nq;
-        wa.m.k = (uint32_t)k;
-        wa.m.out_keys = b->d_keys;
-        wa.m.out_ord = final_arrays ? b->d_ord : nullptr;
-        wa.m.out_score_u32 = b->d_su32;
-        wa.m.out_score = b->d_sf32;
-        wa.m.out_n = b->d_n;
-        wa.tiles = d->d_walk;
-        wa.n_tiles = nt;
-        rc = launch_walk(d->stream, h->tile_docs, wa);
-        if (rc != MSR_OK) return rc;
-        if (!b->untimed) {
-            HIP_TRY(hipEventRecord(b->ev1, d->stream));
-            HIP_TRY(hipEventRecord(b->ev2, d->stream));
-        }
-        ++b->walks;
-        b->last_k = k;
-        b->timed = !b->untimed;
-        return MSR_OK;
-    }
+    sa.unsorted = (b->unsorted_ok && b->ix->shard_ntiles == 1) ? 1u : 0u;  // one tile: its list IS the query's list
+}
+
+// The staged search of a batch, timed or not, over every tile of the handle: the tail of batch_search_local, and with
+// `fa` (the call's doc sets: score_tiles_filtered in the place of score_tiles) the whole of msr_search_filtered's
+// launches. The first `t1` tiles are scored with the full per-tile selection; their merged k-th best key per query is a
+// lower bound on the final k-th key, so the remaining tiles only have to report keys at or above it (theta_select: one
+// pass, usually no survivor). Exact: the final merge sees every key that can be in the top-k; a masked score is 0, so
+// with doc sets the bound holds among the MEMBERS of the query's set. (A launch holds at most 65535 tiles in y; x =
+// queries.) A timed batch gets ev1 between the scoring and the final merge and ev2 after it. `sa`: fill_search_args.
+static int staged_search(msr_batch* b, int k, ScoreArgs sa, bool final_arrays, const FilterArgs* fa) {
+    msr_index* ix = b->ix;
+    DeviceIndex* d = ix->dev;
+    const uint32_t tile_docs = ix->host.h->tile_docs, nt = ix->shard_ntiles;
+    auto score = [&](uint32_t t_begin, uint32_t t_end) {
+        return fa ? launch_score_filtered(d->stream, tile_docs, t_begin, t_end, sa, *fa)
+                  : launch_score(d->stream, tile_docs, t_begin, t_end, sa);
+    };
     uint32_t t1 = nt;
     // (small launches — fewer (tile, query) pairs than one round of resident workgroups — stay in ONE launch: two
     // more kernels in the chain would cost the call more latency than the cheaper selection saves)
     if (nt >= 2 && (uint64_t)nt * (uint64_t)b->nq >= kMinStagedPairs)
         t1 = std::max<uint32_t>(1u, nt / kStage1Fraction);
-    sa.theta = nullptr;
-    sa.unsorted = (b->unsorted_ok && nt == 1) ? 1u : 0u;  // one tile: its list IS the query's list
-    rc = launch_score(d->stream, h->tile_docs, 0, t1, sa);
+    int rc = score(0, t1);
     if (rc != MSR_OK) return rc;
-    if (t1 < nt) {
-        MergeArgs m1;
-        m1.lists = b->d_part;
-        m1.list_stride = (uint64_t)b->nq * k;
-        m1.n_lists = t1;
-        m1.nq = (uint32_t)b->nq;
-        m1.k = (uint32_t)k;
-        m1.out_keys = b->d_keys;
-        m1.out_ord = nullptr;
-        m1.out_score_u32 = nullptr;
-        m1.out_score = nullptr;
-        m1.out_n = nullptr;
-        rc = launch_merge(d->stream, m1);
-        if (rc != MSR_OK) return rc;
-        sa.theta = b->d_keys;
-        rc = launch_score(d->stream, h->tile_docs, t1, nt, sa);
-        if (rc != MSR_OK) return rc;
-    }
-    if (!b->untimed) HIP_TRY(hipEventRecord(b->ev1, d->stream));
     MergeArgs ma;
     ma.lists = b->d_part;
     ma.list_stride = (uint64_t)b->nq * k;
-    ma.n_lists = ix->shard_ntiles;
     ma.nq = (uint32_t)b->nq;
     ma.k = (uint32_t)k;
     ma.out_keys = b->d_keys;
+    if (t1 < nt) {
+        ma.n_lists = t1;
+        ma.out_ord = nullptr;
+        ma.out_score_u32 = nullptr;
+        ma.out_score = nullptr;
+        ma.out_n = nullptr;
+        rc = launch_merge(d->stream, ma);
+        if (rc != MSR_OK) return rc;
+        sa.theta = b->d_keys;
+        rc = score(t1, nt);
+        if (rc != MSR_OK) return rc;
+    }
+    if (!b->untimed) HIP_TRY(hipEventRecord(b->ev1, d->stream));
+    ma.n_lists = nt;
     ma.out_ord = final_arrays ? b->d_ord : nullptr;
     ma.out_score_u32 = b->d_su32;
     ma.out_score = b->d_sf32;
@@ -967,6 +934,44 @@ int batch_search_local(msr_batch* b, int k, bool final_arrays) {
     rc = launch_merge(d->stream, ma);
     if (rc != MSR_OK) return rc;
     if (!b->untimed) HIP_TRY(hipEventRecord(b->ev2, d->stream));
+    b->last_k = k;
+    b->timed = !b->untimed;
+    return MSR_OK;
+}
+
+int batch_search_local(msr_batch* b, int k, bool final_arrays) {
+    msr_index* ix = b->ix;
+    DeviceIndex* d = ix->dev;
+    HIP_TRY(hipSetDevice(d->device));
+    if (!b->untimed)
+        if (int rc0 = batch_begin_timed(b)) return rc0;
+    ScoreArgs sa;
+    fill_search_args(sa, b, k);
+    if (!walk_route(d->d_walk != nullptr, sa.light != 0, b->unsorted_ok, (uint32_t)b->nq, (uint32_t)k))
+        return staged_search(b, k, sa, final_arrays, nullptr);
+    // small index, many light queries: one workgroup per query walks the tiles and writes the result rows itself
+    // (msr_walk.hpp): no per-tile lists, no merge launch. The whole kernel counts as score time.
+    WalkArgs wa;
+    wa.s = sa;
+    wa.m.lists = nullptr;
+    wa.m.list_stride = 0;
+    wa.m.n_lists = 0;
+    wa.m.nq = (uint32_t)b->nq;
+    wa.m.k = (uint32_t)k;
+    wa.m.out_keys = b->d_keys;
+    wa.m.out_ord = final_arrays ? b->d_ord : nullptr;
+    wa.m.out_score_u32 = b->d_su32;
+    wa.m.out_score = b->d_sf32;
+    wa.m.out_n = b->d_n;
+    wa.tiles = d->d_walk;
+    wa.n_tiles = ix->shard_ntiles;
+    const int rc = launch_walk(d->stream, ix->host.h->tile_docs, wa);
+    if (rc != MSR_OK) return rc;
+    if (!b->untimed) {
+        HIP_TRY(hipEventRecord(b->ev1, d->stream));
+        HIP_TRY(hipEventRecord(b->ev2, d->stream));
+    }
+    ++b->walks;
     b->last_k = k;
     b->timed = !b->untimed;
     return MSR_OK;
@@ -1183,12 +1188,7 @@ static int listed_check_shapes(const char* who, const msr_index* ix, bool args_o
         set_error("%s: null t_ord", who);
         return MSR_E_INVAL;
     }
-    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
-        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
-                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
-        return MSR_E_INVAL;
-    }
-    return MSR_OK;
+    return whole_index_check(who, ix);
 }
 
 // ... then the ranges (MSR_E_RANGE): listed docs per query, ordinals (self_ord: msr_rank_docs only, may be null), and
@@ -1213,11 +1213,7 @@ static int listed_check_ranges(const char* who, const msr_index* ix, int nq, con
                       (unsigned long long)n_docs);
             return MSR_E_RANGE;
         }
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
-        return MSR_E_NODEVICE;
-    }
-    return MSR_OK;
+    return device_check(ix);
 }
 
 // ------------------------------------------------------------------------------------------------ exact ranks
@@ -1248,7 +1244,7 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
     msr_batch* b = nullptr;
     rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
     if (rc != MSR_OK) return rc;
-    CallScratch cs(d, b);
+    CallScratch cs(who, d, b);
     // ---- plan: (query, tile) pairs that hold a listed doc or the query's self doc, tile-major; the docs of a pair
     RankPlan pl;
     rank_plan(tile, nq, t_ptr, t_ord, self_ord, pl);
@@ -1260,20 +1256,16 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
     uint32_t max_pe = 0;
     for (int q0 = 0; q0 < nq; q0 += kRankPassQueries)
         max_pe = std::max<uint32_t>(max_pe, (uint32_t)(t_ptr[std::min(nq, q0 + kRankPassQueries)] - t_ptr[q0]));
-    const size_t in_bytes = cs.in.size() * 4, sc_bytes = ((size_t)n_ent + (size_t)nq) * 4, rk_bytes = (size_t)n_ent * 4,
+    const size_t sc_bytes = ((size_t)n_ent + (size_t)nq) * 4, rk_bytes = (size_t)n_ent * 4,
                  part_bytes = std::max<size_t>((size_t)n_tiles * max_pe, 1) * 4;
-    uint32_t *d_in = cs.alloc(in_bytes), *d_sc = cs.alloc(sc_bytes), *d_rk = cs.alloc(rk_bytes), *d_part = cs.alloc(part_bytes);
-    if (!d_in || !d_sc || !d_rk || !d_part) {
+    uint32_t* d_in = cs.upload("listed docs", &rc);
+    if (!d_in) return rc;
+    uint32_t *d_sc = cs.alloc(sc_bytes), *d_rk = cs.alloc(rk_bytes), *d_part = cs.alloc(part_bytes);
+    if (!d_sc || !d_rk || !d_part) {
         set_error("%s: device allocation failed (%zu bytes of per-tile counts)", who, part_bytes);
         return MSR_E_NOMEM;
     }
-    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return MSR_E_HIP;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; ms && i < 3; ++i)
-        if (!(ev[i] = cs.event())) {
-            set_error("%s: hipEventCreate failed", who);
-            return MSR_E_HIP;
-        }
+    if ((rc = cs.laps(3, ms != nullptr))) return rc;
     // ---- launches: the gather over the pairs, then count + reduce per pass of queries
     RankArgs ra;
     fill_score_args(ra.s, b, 1);
@@ -1292,10 +1284,10 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
     ra.e0 = 0;
     ra.pe = 0;
     ra.n_tiles = n_tiles;
-    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(0))) return rc;
     rc = launch_rank(d->stream, tile, false, n_pairs, 0, ra);
     if (rc != MSR_OK) return rc;
-    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(1))) return rc;
     for (int q0 = 0; q0 < nq; q0 += kRankPassQueries) {
         const int q1 = std::min(nq, q0 + kRankPassQueries);
         ra.s.q0 = (uint32_t)q0;
@@ -1308,15 +1300,13 @@ int msr_rank_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, co
         hipLaunchKernelGGL(rank_reduce, dim3((ra.pe + 255) / 256), dim3(256), 0, d->stream, ra);
         if (!hip_ok(who, hipGetLastError(), "rank_reduce")) return MSR_E_HIP;
     }
-    if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(2))) return rc;
     // ---- download
     if (!hip_ok(who, hipStreamSynchronize(d->stream), "the rank kernels") ||
         !hip_ok(who, hipMemcpy(out_rank, d_rk, rk_bytes, hipMemcpyDeviceToHost), "download") ||
         !hip_ok(who, hipMemcpy(out_score_u32, d_sc, (size_t)n_ent * 4, hipMemcpyDeviceToHost), "download"))
         return MSR_E_HIP;
-    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
-               !hip_ok(who, hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
-        return MSR_E_HIP;
+    if (ms && ((rc = cs.elapsed(0, 1, &ms[0])) || (rc = cs.elapsed(1, 2, &ms[1])))) return rc;
     cs.ok = true;
     return MSR_OK;
 }
@@ -1335,19 +1325,12 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
         set_error("%s: bad argument", who);
         return MSR_E_INVAL;
     }
-    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
-        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
-                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
-        return MSR_E_INVAL;
-    }
+    if (int rc0 = whole_index_check(who, ix)) return rc0;
     if (k < 1 || k > MSR_DEEP_KMAX) {
         set_error("%s: k must be in [1, MSR_DEEP_KMAX = %d] (got %d)", who, MSR_DEEP_KMAX, k);
         return MSR_E_RANGE;
     }
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
-        return MSR_E_NODEVICE;
-    }
+    if (int rc0 = device_check(ix)) return rc0;
     if (ms) ms[0] = ms[1] = 0.f;
     if (nq == 0) return MSR_OK;
     const IndexHeader* h = ix->host.h;
@@ -1361,7 +1344,7 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
     msr_batch* b = nullptr;
     int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
     if (rc != MSR_OK) return rc;
-    CallScratch cs(d, b);
+    CallScratch cs(who, d, b);
     // ---- scratch of one pass: the score rows [qt][n_tiles * tile_docs] and the result rows [qt][k]
     const uint32_t qt = (uint32_t)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, kDeepPassBytes / (ld * 4)));
     const size_t s_bytes = (size_t)qt * ld * 4, r_bytes = (size_t)qt * k * 4;
@@ -1371,12 +1354,7 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
         set_error("%s: device allocation failed (%zu bytes of score rows, %u queries per pass)", who, s_bytes, qt);
         return MSR_E_NOMEM;
     }
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; ms && i < 3; ++i)
-        if (!(ev[i] = cs.event())) {
-            set_error("%s: hipEventCreate failed", who);
-            return MSR_E_HIP;
-        }
+    if ((rc = cs.laps(3, ms != nullptr))) return rc;
     double t_score = 0, t_select = 0;
     for (uint32_t q0 = 0; q0 < (uint32_t)nq; q0 += qt) {
         const uint32_t qn = std::min<uint32_t>(qt, (uint32_t)nq - q0);
@@ -1389,10 +1367,10 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
         sa.dump = d_S;
         sa.tpr = h->n_tiles;
         sa.dump_add = 0;
-        if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+        if ((rc = cs.mark(0))) return rc;
         rc = launch_score(d->stream, h->tile_docs, 0, h->n_tiles, sa, true);
         if (rc != MSR_OK) return rc;
-        if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+        if ((rc = cs.mark(1))) return rc;
         DeepArgs da;
         da.src = d_S;
         da.ld = ld;
@@ -1405,7 +1383,7 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
         da.out_n = reinterpret_cast<int32_t*>(d_n);
         rc = launch_deep_select(d->stream, da);
         if (rc != MSR_OK) return rc;
-        if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+        if ((rc = cs.mark(2))) return rc;
         const size_t o = (size_t)q0 * k, nb = (size_t)qn * k * 4;
         if (!hip_ok(who, hipStreamSynchronize(d->stream), "the scoring and selection kernels") ||
             !hip_ok(who, hipMemcpy(out_doc_ord + o, d_idx, nb, hipMemcpyDeviceToHost), "download") ||
@@ -1413,14 +1391,10 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
             (out_score_u32 && !hip_ok(who, hipMemcpy(out_score_u32 + o, d_su, nb, hipMemcpyDeviceToHost), "download")) ||
             !hip_ok(who, hipMemcpy(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost), "download"))
             return MSR_E_HIP;
-        if (ms) {
-            float t0 = 0, t1 = 0;
-            if (!hip_ok(who, hipEventElapsedTime(&t0, ev[0], ev[1]), "hipEventElapsedTime") ||
-                !hip_ok(who, hipEventElapsedTime(&t1, ev[1], ev[2]), "hipEventElapsedTime"))
-                return MSR_E_HIP;
-            t_score += t0;
-            t_select += t1;
-        }
+        float t0 = 0, t1 = 0;
+        if ((rc = cs.elapsed(0, 1, &t0)) || (rc = cs.elapsed(1, 2, &t1))) return rc;
+        t_score += t0;
+        t_select += t1;
     }
     if (ms) ms[0] = (float)t_score, ms[1] = (float)t_select;
     cs.ok = true;
@@ -1428,10 +1402,9 @@ int msr_search_deep(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, 
 }
 
 // ------------------------------------------------------------------------------------------------ filtered search
-// The staged path of batch_search_local restated for score_tiles_filtered: stage 1 over max(1, nt / kStage1Fraction) tiles
-// when the launch is big enough, its merge, the rest of the tiles with the thresholds, the final merge. A masked score is
-// 0, so a threshold of stage 1 is a bound among the MEMBERS of the query's set and stays exact. The call never takes
-// score_tiles_walk and never the zero-copy block of small calls (its batch is an ordinary pooled one).
+// The staged search (staged_search) with score_tiles_filtered in the place of score_tiles, on a batch of the call's own
+// that is timed through its own events when the caller asks for times. The call never takes score_tiles_walk and never
+// the zero-copy block of small calls (its batch is an ordinary pooled one).
 int msr_search_filtered(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w, int nq, int k,
                         uint32_t flags, const uint32_t* set_bits, int n_sets, const int32_t* q_set, uint32_t* out_doc_ord,
                         float* out_score, uint32_t* out_score_u32, int32_t* out_n, float ms[2]) {
@@ -1442,20 +1415,13 @@ int msr_search_filtered(msr_index* ix, const int64_t* q_ptr, const int32_t* q_te
         return MSR_E_INVAL;
     }
     if (int rc0 = filter_check_shapes(who, set_bits, n_sets, q_set)) return rc0;
-    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
-        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
-                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
-        return MSR_E_INVAL;
-    }
+    if (int rc0 = whole_index_check(who, ix)) return rc0;
     if (k < 1 || k > MSR_KMAX) {
         set_error("%s: k must be in [1, MSR_KMAX = %d] (got %d)", who, MSR_KMAX, k);
         return MSR_E_RANGE;
     }
     if (int rc0 = filter_check_ranges(who, n_sets, q_set, nq)) return rc0;
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU scoring path");
-        return MSR_E_NODEVICE;
-    }
+    if (int rc0 = device_check(ix)) return rc0;
     if (ms) ms[0] = ms[1] = 0.f;
     if (nq == 0) return MSR_OK;
     const IndexHeader* h = ix->host.h;
@@ -1468,73 +1434,29 @@ int msr_search_filtered(msr_index* ix, const int64_t* q_ptr, const int32_t* q_te
     msr_batch* b = nullptr;
     int rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, k, flags, 0, 0, &b);
     if (rc != MSR_OK) return rc;
-    CallScratch cs(d, b);
+    CallScratch cs(who, d, b);
     // ---- the doc sets: bitmap | any | q_set, one block
     FilterImage fi;
     fi.build(set_bits, n_sets, q_set, nq, h->n_docs, h->tile_docs, h->n_tiles);
     const size_t o_bits = cs.put(fi.bits), o_any = cs.put(fi.any), o_qs = cs.put(fi.q_set);
-    const size_t in_bytes = cs.in.size() * 4;
-    uint32_t* d_in = cs.alloc(in_bytes);
-    if (!d_in) {
-        set_error("%s: device allocation failed (%zu bytes of doc sets)", who, in_bytes);
-        return MSR_E_NOMEM;
-    }
-    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the doc sets")) return MSR_E_HIP;
+    const uint32_t* d_in = cs.upload("doc sets", &rc);
+    if (!d_in) return rc;
     FilterArgs fa;
     fa.bits = d_in + o_bits;
     fa.any = reinterpret_cast<const uint8_t*>(d_in + o_any);
     fa.q_set = reinterpret_cast<const int32_t*>(d_in + o_qs);
     fa.stride = fi.stride;
     fa.n_tiles = h->n_tiles;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; ms && i < 3; ++i)
-        if (!(ev[i] = cs.event())) {
-            set_error("%s: hipEventCreate failed", who);
-            return MSR_E_HIP;
-        }
-    // ---- launches
+    // ---- launches, then the download (msr_batch_fetch waits for the stream)
+    b->untimed = ms == nullptr;
+    if (ms && (rc = batch_begin_timed(b))) return rc;
     ScoreArgs sa;
-    fill_score_args(sa, b, k);
-    sa.light = b->max_sparse_terms <= 64 ? 1u : 0u;
-    const uint32_t nt = ix->shard_ntiles;
-    uint32_t t1 = nt;
-    if (nt >= 2 && (uint64_t)nt * (uint64_t)nq >= kMinStagedPairs) t1 = std::max<uint32_t>(1u, nt / kStage1Fraction);
-    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
-    rc = launch_score_filtered(d->stream, h->tile_docs, 0, t1, sa, fa);
-    if (rc != MSR_OK) return rc;
-    MergeArgs ma;
-    ma.lists = b->d_part;
-    ma.list_stride = (uint64_t)nq * k;
-    ma.nq = (uint32_t)nq;
-    ma.k = (uint32_t)k;
-    ma.out_keys = b->d_keys;
-    if (t1 < nt) {
-        ma.n_lists = t1;
-        ma.out_ord = nullptr;
-        ma.out_score_u32 = nullptr;
-        ma.out_score = nullptr;
-        ma.out_n = nullptr;
-        rc = launch_merge(d->stream, ma);
-        if (rc != MSR_OK) return rc;
-        sa.theta = b->d_keys;
-        rc = launch_score_filtered(d->stream, h->tile_docs, t1, nt, sa, fa);
-        if (rc != MSR_OK) return rc;
-    }
-    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
-    ma.n_lists = nt;
-    ma.out_ord = b->d_ord;
-    ma.out_score_u32 = b->d_su32;
-    ma.out_score = b->d_sf32;
-    ma.out_n = b->d_n;
-    rc = launch_merge(d->stream, ma);
-    if (rc != MSR_OK) return rc;
-    if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
-    // ---- download (msr_batch_fetch waits for the stream)
-    b->last_k = k;
+    fill_search_args(sa, b, k);
+    if ((rc = staged_search(b, k, sa, true, &fa))) return rc;
     rc = msr_batch_fetch(b, out_doc_ord, out_score, out_score_u32, out_n);
     if (rc != MSR_OK) return rc;
-    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime") ||
-               !hip_ok(who, hipEventElapsedTime(&ms[1], ev[1], ev[2]), "hipEventElapsedTime")))
+    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[0], b->ev0, b->ev1), "hipEventElapsedTime") ||
+               !hip_ok(who, hipEventElapsedTime(&ms[1], b->ev1, b->ev2), "hipEventElapsedTime")))
         return MSR_E_HIP;
     cs.ok = true;
     return MSR_OK;
@@ -1587,7 +1509,7 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
     msr_batch* b = nullptr;
     rc = batch_create_impl(ix, q_ptr, q_term, q_w, nq, 1, flags, 0, 0, &b);
     if (rc != MSR_OK) return rc;
-    CallScratch cs(d, b);
+    CallScratch cs(who, d, b);
     // ---- plan: the tables the kernel reads. A repeated target of a query is listed once; its row is copied below,
     // after the download
     ExplainPlan pl;
@@ -1595,19 +1517,15 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
     const uint32_t n_pairs = (uint32_t)(pl.pairs.size() / 4);
     // ---- upload, one block: pairs (uint4) | items (uint2) | entry ranges (uint2) | entries (uint2)
     const size_t o_pairs = cs.put(pl.pairs), o_items = cs.put(pl.items), o_qr = cs.put(pl.q_range), o_ents = cs.put(pl.ents);
-    const size_t in_bytes = cs.in.size() * 4, out_bytes = (size_t)need * 4;
-    uint32_t *d_in = cs.alloc(in_bytes), *d_out = cs.alloc(out_bytes);
-    if (!d_in || !d_out) {
+    const size_t out_bytes = (size_t)need * 4;
+    const uint32_t* d_in = cs.upload("listed docs", &rc);
+    if (!d_in) return rc;
+    uint32_t* d_out = cs.alloc(out_bytes);
+    if (!d_out) {
         set_error("%s: device allocation failed (%zu bytes of doc weights)", who, out_bytes);
         return MSR_E_NOMEM;
     }
-    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return MSR_E_HIP;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (int i = 0; ms && i < 2; ++i)
-        if (!(ev[i] = cs.event())) {
-            set_error("%s: hipEventCreate failed", who);
-            return MSR_E_HIP;
-        }
+    if ((rc = cs.laps(2, ms != nullptr))) return rc;
     // ---- launches: the output zeroed, then explain_tiles over the pairs
     ExplainArgs xa;
     xa.seg_ptr = d->d_seg_ptr;
@@ -1621,16 +1539,16 @@ int msr_explain_docs(msr_index* ix, const int64_t* q_ptr, const int32_t* q_term,
     xa.q_range = reinterpret_cast<const uint2*>(d_in + o_qr);
     xa.ents = reinterpret_cast<const uint2*>(d_in + o_ents);
     xa.out = d_out;
-    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(0))) return rc;
     if (!hip_ok(who, hipMemsetAsync(d_out, 0, out_bytes, d->stream), "hipMemsetAsync")) return MSR_E_HIP;
     rc = launch_explain(d->stream, ix->host.h->tile_docs, n_pairs, xa);
     if (rc != MSR_OK) return rc;
-    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(1))) return rc;
     // ---- download
     if (!hip_ok(who, hipStreamSynchronize(d->stream), "the explain kernel") ||
         !hip_ok(who, hipMemcpy(out_doc_w, d_out, out_bytes, hipMemcpyDeviceToHost), "download"))
         return MSR_E_HIP;
-    if (ms && !hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime")) return MSR_E_HIP;
+    if ((rc = cs.elapsed(0, 1, ms))) return rc;
     for (const auto& dp : pl.dups) {  // a repeated target: the row of the entry it repeats
         const uint32_t q = (uint32_t)(std::upper_bound(t_ptr, t_ptr + nq + 1, (int64_t)dp.first) - t_ptr - 1);
         memcpy(out_doc_w + pl.x_off[dp.first], out_doc_w + pl.x_off[dp.second], (size_t)(q_ptr[q + 1] - q_ptr[q]) * 4);
@@ -1663,40 +1581,30 @@ int msr_doc_vectors(msr_index* ix, const uint32_t* t_ord, int64_t n, int64_t* ou
                       (unsigned long long)h->n_docs);
             return MSR_E_RANGE;
         }
-    if (ix->term_nshards > 0 || ix->shard_ntiles != h->n_tiles) {
-        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
-                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
-        return MSR_E_INVAL;
-    }
-    if (!ix->dev) {
-        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU path to the doc vectors");
-        return MSR_E_NODEVICE;
-    }
+    if (int rc0 = whole_index_check(who, ix)) return rc0;
+    if (int rc0 = device_check(ix, "path to the doc vectors")) return rc0;
     if (ms) ms[0] = ms[1] = ms[2] = 0.f;
     out_ptr[0] = 0;
     *n_entries = 0;
     if (n == 0) return MSR_OK;
     DeviceIndex* d = ix->dev;
-    CallScratch cs(d);
+    CallScratch cs(who, d);
     // ---- plan: the distinct listed docs in ordinal order (the rows of the device output), (tile, stripe) work items
     DocvecPlan pl;
     docvec_plan(ix->host.seg_ptr, h->n_terms, h->tile_docs, t_ord, n, pl);
     const uint32_t rows = (uint32_t)pl.ords.size(), n_work = (uint32_t)(pl.work.size() / 4);
     // ---- upload, one block: work items (uint4) | row ordinals | dense-head terms
     const size_t o_work = cs.put(pl.work), o_ords = cs.put(pl.ords), o_dt = cs.put(ix->host.dense_terms, h->n_dense);
-    const size_t in_bytes = cs.in.size() * 4, len_bytes = (size_t)rows * 4, ptr_bytes = ((size_t)rows + 1) * 4;
-    uint32_t *d_in = cs.alloc(in_bytes), *d_len = cs.alloc(len_bytes), *d_ptr = cs.alloc(ptr_bytes);
-    if (!d_in || !d_len || !d_ptr) {
+    const size_t len_bytes = (size_t)rows * 4, ptr_bytes = ((size_t)rows + 1) * 4;
+    int rc = MSR_OK;
+    const uint32_t* d_in = cs.upload("listed docs", &rc);
+    if (!d_in) return rc;
+    uint32_t *d_len = cs.alloc(len_bytes), *d_ptr = cs.alloc(ptr_bytes);
+    if (!d_len || !d_ptr) {
         set_error("%s: device allocation failed (%zu bytes of row lengths)", who, len_bytes);
         return MSR_E_NOMEM;
     }
-    if (!hip_ok(who, hipMemcpy(d_in, cs.in.data(), in_bytes, hipMemcpyHostToDevice), "upload of the listed docs")) return MSR_E_HIP;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // count | fill | ordering, the host's part between
-    for (int i = 0; ms && i < 5; ++i)
-        if (!(ev[i] = cs.event())) {
-            set_error("%s: hipEventCreate failed", who);
-            return MSR_E_HIP;
-        }
+    if ((rc = cs.laps(5, ms != nullptr))) return rc;  // count | fill | ordering, the host's part between
     DocvecArgs va;
     va.seg_ptr = d->d_seg_ptr;
     va.postings = d->d_postings;
@@ -1714,16 +1622,16 @@ int msr_doc_vectors(msr_index* ix, const uint32_t* t_ord, int64_t n, int64_t* ou
     va.ptr = d_ptr;
     va.term = va.w = va.out_term = va.out_w = nullptr;
     // ---- count pass; the row lengths come back and are prefix-summed on the host
-    if (ms && !hip_ok(who, hipEventRecord(ev[0], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(0))) return rc;
     if (!hip_ok(who, hipMemsetAsync(d_len, 0, len_bytes, d->stream), "hipMemsetAsync")) return MSR_E_HIP;
-    int rc = launch_docvec(d->stream, false, n_work, va);
+    rc = launch_docvec(d->stream, false, n_work, va);
     if (rc != MSR_OK) return rc;
-    if (ms && !hip_ok(who, hipEventRecord(ev[1], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(1))) return rc;
     std::vector<uint32_t> row_ptr((size_t)rows + 1, 0u);  // (lengths first, then the exclusive prefix sum)
     if (!hip_ok(who, hipStreamSynchronize(d->stream), "the count pass") ||
         !hip_ok(who, hipMemcpy(row_ptr.data() + 1, d_len, len_bytes, hipMemcpyDeviceToHost), "download of the row lengths"))
         return MSR_E_HIP;
-    if (ms && !hip_ok(who, hipEventElapsedTime(&ms[0], ev[0], ev[1]), "hipEventElapsedTime")) return MSR_E_HIP;
+    if ((rc = cs.elapsed(0, 1, ms))) return rc;
     uint64_t total = 0;
     for (int64_t e = 0; e < n; ++e) {
         total += row_ptr[(size_t)pl.row_of[(size_t)e] + 1];
@@ -1755,16 +1663,16 @@ int msr_doc_vectors(msr_index* ix, const uint32_t* t_ord, int64_t n, int64_t* ou
     if (!hip_ok(who, hipMemcpyAsync(d_ptr, row_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, d->stream), "upload of the row starts") ||
         !hip_ok(who, hipMemsetAsync(d_len, 0, len_bytes, d->stream), "hipMemsetAsync"))
         return MSR_E_HIP;
-    if (ms && !hip_ok(who, hipEventRecord(ev[2], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(2))) return rc;
     rc = launch_docvec(d->stream, true, n_work, va);
     if (rc != MSR_OK) return rc;
-    if (ms && !hip_ok(who, hipEventRecord(ev[3], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(3))) return rc;
     for (uint32_t r0 = 0; r0 < rows; r0 += kRankMaxGridX) {
         va.row0 = r0;
         hipLaunchKernelGGL(docvec_order, dim3(std::min<uint32_t>(kRankMaxGridX, rows - r0)), dim3(256), 0, d->stream, va);
         if (!hip_ok(who, hipGetLastError(), "docvec_order")) return MSR_E_HIP;
     }
-    if (ms && !hip_ok(who, hipEventRecord(ev[4], d->stream), "hipEventRecord")) return MSR_E_HIP;
+    if ((rc = cs.mark(4))) return rc;
     // ---- download: straight into the caller's arrays when the list is the rows (ascending, no duplicate), else row by row
     if (!hip_ok(who, hipStreamSynchronize(d->stream), "the fill and ordering passes")) return MSR_E_HIP;
     bool same = rows == (uint64_t)n;
@@ -1784,9 +1692,7 @@ int msr_doc_vectors(msr_index* ix, const uint32_t* t_ord, int64_t n, int64_t* ou
         memcpy(out_term + out_ptr[e], ht.data() + row_ptr[r], len * 4);
         memcpy(out_w + out_ptr[e], hw.data() + row_ptr[r], len * 4);
     }
-    if (ms && (!hip_ok(who, hipEventElapsedTime(&ms[1], ev[2], ev[3]), "hipEventElapsedTime") ||
-               !hip_ok(who, hipEventElapsedTime(&ms[2], ev[3], ev[4]), "hipEventElapsedTime")))
-        return MSR_E_HIP;
+    if (ms && ((rc = cs.elapsed(2, 3, &ms[1])) || (rc = cs.elapsed(3, 4, &ms[2])))) return rc;
     cs.ok = true;
     return MSR_OK;
 }

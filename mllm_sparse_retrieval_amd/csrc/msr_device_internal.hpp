@@ -341,6 +341,25 @@ inline int filter_check_ranges(const char* who, int n_sets, const int32_t* q_set
     return MSR_OK;
 }
 
+// The refusal of the calls that read the whole index (listed docs, deep and filtered search, doc vectors) on a shard handle
+inline int whole_index_check(const char* who, const msr_index* ix) {
+    if (ix->term_nshards > 0 || ix->shard_ntiles != ix->host.h->n_tiles) {
+        set_error("%s: the call needs every doc and every term of the index; this handle is a %s shard (open the whole "
+                  "index with msr_index_open)", who, ix->term_nshards > 0 ? "term-range" : "doc-range");
+        return MSR_E_INVAL;
+    }
+    return MSR_OK;
+}
+
+// ... and of every device call on a handle opened without a device; `missing` names the CPU path there is none of
+inline int device_check(const msr_index* ix, const char* missing = "scoring path") {
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound (opened with device < 0); there is no CPU %s", missing);
+        return MSR_E_NODEVICE;
+    }
+    return MSR_OK;
+}
+
 // defined in msr_device.hip
 int launch_select(hipStream_t st, uint32_t tile_docs, const SelectArgs& a);
 int launch_merge(hipStream_t st, const MergeArgs& a);
@@ -399,12 +418,14 @@ void fill_score_args(msr::ScoreArgs& sa, msr_batch* b, int k);  // a launch over
 // call's batch. Leaving the scope waits for the stream unless the call set `ok` (nothing in flight may still use the
 // scratch), then gives the blocks back to the pool, the events back to the handle and frees the batch, in this order.
 struct CallScratch {
+    const char* who;  // the call, as its error messages name it
     msr::DeviceIndex* d;
     msr_batch* b;
     bool ok = false;  // the call succeeded: its last step waited for the stream already
     std::vector<std::pair<void*, size_t>> blocks;
-    std::vector<hipEvent_t> events;
-    explicit CallScratch(msr::DeviceIndex* dev, msr_batch* batch = nullptr) : d(dev), b(batch) {}
+    std::vector<hipEvent_t> events;  // the call's laps, when it is timed
+    bool timed = false;
+    CallScratch(const char* name, msr::DeviceIndex* dev, msr_batch* batch = nullptr) : who(name), d(dev), b(batch) {}
     CallScratch(const CallScratch&) = delete;
     CallScratch& operator=(const CallScratch&) = delete;
     ~CallScratch() {
@@ -426,9 +447,41 @@ struct CallScratch {
         if (p) blocks.emplace_back(p, bytes);
         return (uint32_t*)p;
     }
-    hipEvent_t event() {  // null: hipEventCreate failed
-        hipEvent_t e = d->borrow_event();
-        if (e) events.push_back(e);
-        return e;
+    // The block built with put(), copied to the device (`what` names its content in the messages). Null: *rc and the
+    // error are set.
+    uint32_t* upload(const char* what, int* rc) {
+        const size_t bytes = in.size() * 4;
+        uint32_t* p = alloc(bytes);
+        if (!p) {
+            msr::set_error("%s: device allocation failed (%zu bytes of %s)", who, bytes, what);
+            *rc = MSR_E_NOMEM;
+            return nullptr;
+        }
+        const hipError_t e = hipMemcpy(p, in.data(), bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) return p;
+        msr::set_error("%s: upload of the %s failed: %s", who, what, hipGetErrorString(e));
+        *rc = MSR_E_HIP;
+        return nullptr;
+    }
+    // The call's timing laps: laps(n, want) borrows n events when the caller asked for times, mark(i) records event i on
+    // the stream, elapsed(i, j, out) reads the milliseconds from mark i to mark j. An untimed call does nothing in the
+    // last two. Each returns the call's error code.
+    int laps(int n, bool want) {
+        timed = want;
+        for (int i = 0; timed && i < n; ++i) {
+            hipEvent_t e = d->borrow_event();
+            if (!e) {
+                msr::set_error("%s: hipEventCreate failed", who);
+                return MSR_E_HIP;
+            }
+            events.push_back(e);
+        }
+        return MSR_OK;
+    }
+    int mark(int i) {
+        return !timed || msr::hip_ok(who, hipEventRecord(events[i], d->stream), "hipEventRecord") ? MSR_OK : MSR_E_HIP;
+    }
+    int elapsed(int i, int j, float* out) {
+        return !timed || msr::hip_ok(who, hipEventElapsedTime(out, events[i], events[j]), "hipEventElapsedTime") ? MSR_OK : MSR_E_HIP;
     }
 };

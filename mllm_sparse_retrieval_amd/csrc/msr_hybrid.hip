@@ -353,48 +353,100 @@ static int dense_pass_scores(msr_dense* dx, const DensePasses& ps, const void* q
                    : launch_dense_gemm(dx, dx->d_P, (const _Float16*)d_Q, d_S, qn, qn_pad, ps.n_cover, dx->n_pad, dx->stream);
 }
 
-// to_device = true: out_* are DEVICE buffers ([nq][k] / [nq]) filled on dx->stream (hybrid path); else host buffers.
-// q: [nq][h] fp16 (uint16_t) or, on an f32 handle, f32 rows.
-static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
-                             int32_t* out_n, float* gemm_ms, float* select_ms, bool to_device, bool unsorted = false) {
-    if (!dx || nq < 0 || (nq && !q_host) || !out_idx || !out_key || !out_n) {
-        set_error("msr_dense_search: bad argument");
-        return MSR_E_INVAL;
+}  // extern "C"
+
+// The pass loop of every dense call: queries go through the GEMM `ps.qt` at a time, and per pass the caller's `stage`
+// turns the pass's key rows into its result, which its `fetch` copies back. Use: begin() (device, passes, the query and
+// score scratch), the caller's own scratch slots, ready(), run().
+struct DensePassLoop {
+    msr_dense* dx;
+    const char* who;           // the call, as its error messages name it
+    bool time_upload = true;   // e0 before the query upload (false: after it, msr_dense_search's gemm_ms)
+    const char* failed = nullptr;  // subject of the failure message when it is not "<who>:"
+    DensePasses ps{};
+    uint8_t* d_Q = nullptr;
+    uint32_t* d_S = nullptr;
+    DensePassLoop(msr_dense* handle, const char* name) : dx(handle), who(name) {}
+
+    int begin(int nq) {
+        HIP_TRY(hipSetDevice(dx->device));
+        ps = dense_passes(dx, nq);
+        // device scratch and events live on the handle (only ever grown): at the reference's --batch_size 2
+        // (scripts/search.sh:29) seven hipMalloc / hipFree pairs per call cost more than the search
+        d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
+        d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
+        return MSR_OK;
     }
-    if (k < 1 || k > MSR_KMAX) {
-        set_error("k must be in [1, %d] (got %d)", MSR_KMAX, k);
-        return MSR_E_RANGE;
+    // `own`: the caller got its own slots. False: something is missing (the caller reports it, MSR_E_NOMEM).
+    bool ready(bool own) {
+        bool ok = d_Q && d_S && own;
+        for (hipEvent_t& e : dx->ev)
+            if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
+        return ok;
     }
-    HIP_TRY(hipSetDevice(dx->device));
-    const DensePasses ps = dense_passes(dx, nq);
-    const uint32_t qt = ps.qt;
-    int rc = MSR_OK;
-    const size_t perq = std::max<size_t>((size_t)qt * k, 1);
-    // device scratch and events live on the handle (only ever grown): at the reference's --batch_size 2
-    // (scripts/search.sh:29) seven hipMalloc / hipFree pairs per call cost more than the search
-    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
-    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
-    uint64_t* d_part = (uint64_t*)dx->take(msr_dense::S_PART, (size_t)dx->n_tiles * perq * 8);
-    uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perq * 4);
-    uint32_t* d_su = (uint32_t*)dx->take(msr_dense::S_SU, perq * 4);
-    float* d_sf = (float*)dx->take(msr_dense::S_SF, perq * 4);
-    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_N, (size_t)qt * 4);
-    bool ok = d_Q && d_S && d_part && d_ord && d_su && d_sf && d_n;
-    for (hipEvent_t& e : dx->ev)
-        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
-    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
-    if (!ok) {
-        set_error("device allocation failed in msr_dense_search (%u queries per pass x %llu docs)", qt, (unsigned long long)dx->n_pad);
-        rc = MSR_E_NOMEM;
+    // prologue(q0, qn, &skip) -> rc runs before the pass's upload and may skip the pass, GEMM included;
+    // stage(q0, qn, d_S) -> rc enqueues the pass's kernels; fetch(q0, qn) -> bool enqueues its copies back.
+    // ms0 / ms1 (may be null): GEMM and stage milliseconds, summed over the passes.
+    template <class Prologue, class Stage, class Fetch>
+    int run(const void* q_host, int nq, float* ms0, float* ms1, Prologue prologue, Stage stage, Fetch fetch) {
+        hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
+        const int qt = (int)ps.qt;
+        double t_gemm = 0, t_stage = 0;
+        int rc = MSR_OK;
+        for (int q0 = 0; q0 < nq && rc == MSR_OK; q0 += qt) {
+            const uint32_t qn = (uint32_t)std::min(qt, nq - q0);
+            bool skip = false;
+            rc = prologue(q0, qn, &skip);
+            if (rc != MSR_OK || skip) continue;
+            rc = dense_pass_scores(dx, ps, q_host, q0, qn, d_Q, d_S, e0, time_upload, who);
+            if (rc != MSR_OK) break;
+            (void)hipEventRecord(e1, dx->stream);
+            rc = stage(q0, qn, d_S);
+            if (rc != MSR_OK) break;
+            (void)hipEventRecord(e2, dx->stream);
+            if (!fetch(q0, qn) || hipStreamSynchronize(dx->stream) != hipSuccess) {
+                set_error("%s%s kernels or result download failed: %s", failed ? failed : who, failed ? "" : ":",
+                          hipGetErrorString(hipGetLastError()));
+                rc = MSR_E_HIP;
+                break;
+            }
+            float a = 0, b = 0;
+            (void)hipEventElapsedTime(&a, e0, e1);
+            (void)hipEventElapsedTime(&b, e1, e2);
+            t_gemm += a;
+            t_stage += b;
+        }
+        if (ms0) *ms0 = (float)t_gemm;
+        if (ms1) *ms1 = (float)t_stage;
+        return rc;
     }
-    double t_gemm = 0, t_sel = 0;
-    for (int q0 = 0; q0 < nq && rc == MSR_OK; q0 += (int)qt) {
-        const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
-        rc = dense_pass_scores(dx, ps, q_host, q0, qn, d_Q, d_S, e0, false, "msr_dense_search");
-        if (rc != MSR_OK) break;
-        (void)hipEventRecord(e1, dx->stream);
+    template <class Stage, class Fetch>
+    int run(const void* q_host, int nq, float* ms0, float* ms1, Stage stage, Fetch fetch) {
+        return run(q_host, nq, ms0, ms1, [](int, uint32_t, bool*) { return (int)MSR_OK; }, stage, fetch);
+    }
+};
+
+// The per-tile lists and the result rows of a pass of the plain and the filtered search, on the handle's slots: take(),
+// then per pass stage() (select_tiles, or select_tiles_filtered with the call's doc sets, then the merge) and fetch().
+struct DenseLists {
+    msr_dense* dx;
+    int k;
+    uint64_t* d_part = nullptr;
+    uint32_t *d_ord = nullptr, *d_su = nullptr;
+    float* d_sf = nullptr;
+    int32_t* d_n = nullptr;
+    bool take(uint32_t qt) {
+        const size_t perq = (size_t)qt * k;
+        d_part = (uint64_t*)dx->take(msr_dense::S_PART, (size_t)dx->n_tiles * perq * 8);
+        d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perq * 4);
+        d_su = (uint32_t*)dx->take(msr_dense::S_SU, perq * 4);
+        d_sf = (float*)dx->take(msr_dense::S_SF, perq * 4);
+        d_n = (int32_t*)dx->take(msr_dense::S_N, (size_t)qt * 4);
+        return d_part && d_ord && d_su && d_sf && d_n;
+    }
+    // fa = null: launch_select, with `unsorted` on a one-tile handle (the fusion takes the list as a set)
+    int stage(int q0, uint32_t qn, const uint32_t* d_S, bool unsorted, const FilterArgs* fa) const {
         SelectArgs se;
-        se.unsorted = 0;
         se.src = d_S;
         se.part = d_part;
         se.n_docs = dx->n;
@@ -402,12 +454,12 @@ static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, u
         se.tpr = dx->n_tiles;
         se.rank = 0;
         se.nq = qn;
-        se.q0 = 0;
+        se.q0 = fa ? (uint32_t)q0 : 0u;  // filtered: the pass's first query in the call (q_set is indexed by q0 + qi, `part` by qi)
         se.qn = qn;
         se.k = (uint32_t)k;
-        se.unsorted = (unsorted && dx->n_tiles == 1) ? 1u : 0u;  // the fusion takes the list as a set
-        rc = launch_select(dx->stream, dx->tile_docs, se);
-        if (rc != MSR_OK) break;
+        se.unsorted = (unsorted && dx->n_tiles == 1) ? 1u : 0u;
+        int rc = fa ? launch_select_filtered(dx->stream, dx->tile_docs, se, *fa) : launch_select(dx->stream, dx->tile_docs, se);
+        if (rc != MSR_OK) return rc;
         MergeArgs ma;
         ma.lists = d_part;
         ma.list_stride = (uint64_t)qn * k;
@@ -419,29 +471,64 @@ static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, u
         ma.out_score_u32 = d_su;
         ma.out_score = d_sf;
         ma.out_n = d_n;
-        rc = launch_merge(dx->stream, ma);
-        if (rc != MSR_OK) break;
-        (void)hipEventRecord(e2, dx->stream);
-        const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_ord, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_key + (size_t)q0 * k, d_su, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, kind, dx->stream) == hipSuccess &&
-                       hipStreamSynchronize(dx->stream) == hipSuccess;
-        if (!c) {
-            set_error("dense search kernels or result download failed: %s", hipGetErrorString(hipGetLastError()));
-            rc = MSR_E_HIP;
-            break;
-        }
-        float a = 0, b2 = 0;
-        (void)hipEventElapsedTime(&a, e0, e1);
-        (void)hipEventElapsedTime(&b2, e1, e2);
-        t_gemm += a;
-        t_sel += b2;
+        return launch_merge(dx->stream, ma);
     }
-    if (gemm_ms) *gemm_ms = (float)t_gemm;
-    if (select_ms) *select_ms = (float)t_sel;
-    return rc;
+    bool fetch(int q0, uint32_t qn, uint32_t* out_idx, uint32_t* out_key, int32_t* out_n, hipMemcpyKind kind) const {
+        return hipMemcpyAsync(out_idx + (size_t)q0 * k, d_ord, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
+               hipMemcpyAsync(out_key + (size_t)q0 * k, d_su, (size_t)qn * k * 4, kind, dx->stream) == hipSuccess &&
+               hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, kind, dx->stream) == hipSuccess;
+    }
+};
+
+// The refusal of queries in the other precision than the handle's rows
+static int dense_precision_check(const char* who, const msr_dense* dx, int q_is_f32) {
+    if ((q_is_f32 != 0) == dx->f32) return MSR_OK;
+    if (dx->f32)
+        set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
+                  "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
+    else
+        set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
+                  "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
+    return MSR_E_INVAL;
 }
+
+// ... and of a handle without a device
+static int dense_device_check(const char* who, const msr_dense* dx) {
+    if (dx->device >= 0) return MSR_OK;
+    set_error("%s: the dense handle has no HIP device; there is no CPU dense search path", who);
+    return MSR_E_NODEVICE;
+}
+
+// to_device = true: out_* are DEVICE buffers ([nq][k] / [nq]) filled on dx->stream (hybrid path); else host buffers.
+// q: [nq][h] fp16 (uint16_t) or, on an f32 handle, f32 rows. gemm_ms starts after the query upload.
+static int dense_search_impl(msr_dense* dx, const void* q_host, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
+                             int32_t* out_n, float* gemm_ms, float* select_ms, bool to_device, bool unsorted = false) {
+    if (!dx || nq < 0 || (nq && !q_host) || !out_idx || !out_key || !out_n) {
+        set_error("msr_dense_search: bad argument");
+        return MSR_E_INVAL;
+    }
+    if (k < 1 || k > MSR_KMAX) {
+        set_error("k must be in [1, %d] (got %d)", MSR_KMAX, k);
+        return MSR_E_RANGE;
+    }
+    DensePassLoop lp(dx, "msr_dense_search");
+    lp.time_upload = false;
+    lp.failed = "dense search";
+    if (int rc = lp.begin(nq)) return rc;
+    DenseLists ls{dx, k};
+    if (!lp.ready(ls.take(lp.ps.qt))) {
+        set_error("device allocation failed in msr_dense_search (%u queries per pass x %llu docs)", lp.ps.qt, (unsigned long long)dx->n_pad);
+        if (gemm_ms) *gemm_ms = 0.f;
+        if (select_ms) *select_ms = 0.f;
+        return MSR_E_NOMEM;
+    }
+    const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    return lp.run(q_host, nq, gemm_ms, select_ms,
+                  [&](int q0, uint32_t qn, const uint32_t* d_S) { return ls.stage(q0, qn, d_S, unsorted, nullptr); },
+                  [&](int q0, uint32_t qn) { return ls.fetch(q0, qn, out_idx, out_key, out_n, kind); });
+}
+
+extern "C" {
 
 int msr_dense_stats(const msr_dense* dx, uint64_t out[4]) {
     if (!dx || !out) {
@@ -475,7 +562,7 @@ int msr_dense_search_f32(msr_dense* dx, const float* q, int nq, int k, uint32_t*
     return dense_search_impl(dx, q, nq, k, out_idx, out_key, out_n, gemm_ms, select_ms, false);
 }
 
-// Exact ranks of listed rows: the passes and the GEMM of the search (dense_passes / dense_pass_scores), then ONE count
+// Exact ranks of listed rows: the pass loop and the GEMM of the search (DensePassLoop), then ONE count
 // kernel per pass over the score rows (msr_dense_rank.hpp) in the place of select + merge. Per pass one upload
 // {t_ptr rebased to the pass | self | the pass's slice of t_row} and the ranks and keys of its entries back.
 int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, const int64_t* t_ptr, const uint32_t* t_row,
@@ -500,15 +587,7 @@ int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, cons
         set_error("%s: null t_row / out_rank / out_key with %lld listed rows", who, (long long)n_ent);
         return MSR_E_INVAL;
     }
-    if ((q_is_f32 != 0) != dx->f32) {
-        if (dx->f32)
-            set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
-                      "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
-        else
-            set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
-                      "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
-        return MSR_E_INVAL;
-    }
+    if (int rc0 = dense_precision_check(who, dx, q_is_f32)) return rc0;
     for (int i = 0; i < nq; ++i) {
         if (t_ptr[i + 1] - t_ptr[i] > MSR_DENSE_RANK_MAX_TARGETS) {
             set_error("%s: query %d lists %lld rows, at most MSR_DENSE_RANK_MAX_TARGETS = %d", who, i,
@@ -529,76 +608,62 @@ int msr_dense_rank_rows(msr_dense* dx, const void* q, int q_is_f32, int nq, cons
     if (ms) ms[0] = ms[1] = 0.f;
     if (nq == 0 || n_ent == 0) return MSR_OK;
     // ---- scratch of the largest pass
-    HIP_TRY(hipSetDevice(dx->device));
-    const DensePasses ps = dense_passes(dx, nq);
-    const int qt = (int)ps.qt;
+    DensePassLoop lp(dx, who);
+    if (int rc = lp.begin(nq)) return rc;
+    const int qt = (int)lp.ps.qt;
     int64_t max_pe = 0;
     for (int q0 = 0; q0 < nq; q0 += qt) max_pe = std::max<int64_t>(max_pe, t_ptr[std::min(nq, q0 + qt)] - t_ptr[q0]);
-    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
-    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
     uint32_t* d_in = (uint32_t*)dx->take(msr_dense::S_RANK_IN, ((size_t)2 * qt + 1 + (size_t)max_pe) * 4);
     uint32_t* d_out = (uint32_t*)dx->take(msr_dense::S_RANK_OUT, (size_t)2 * max_pe * 4);
-    bool ok = d_Q && d_S && d_in && d_out;
-    for (hipEvent_t& e : dx->ev)
-        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
-    if (!ok) {
+    if (!lp.ready(d_in && d_out)) {
         set_error("device allocation failed in %s (%d queries per pass x %llu docs)", who, qt, (unsigned long long)dx->n_pad);
         return MSR_E_NOMEM;
     }
-    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
     std::vector<uint32_t> in;  // host image of the pass's upload
-    double t_gemm = 0, t_count = 0;
-    for (int q0 = 0; q0 < nq; q0 += qt) {
-        const uint32_t qn = (uint32_t)std::min(qt, nq - q0);
-        const int64_t ent0 = t_ptr[q0];
-        const uint32_t pe = (uint32_t)(t_ptr[q0 + qn] - ent0);
-        if (pe == 0) continue;  // nothing listed in this pass: no GEMM either
-        in.assign((size_t)2 * qn + 1 + pe, 0u);
-        uint32_t t_max = 0;
-        for (uint32_t i = 0; i <= qn; ++i) in[i] = (uint32_t)(t_ptr[q0 + i] - ent0);
-        for (uint32_t i = 0; i < qn; ++i) {
-            in[qn + 1 + i] = (uint32_t)(self_row ? std::max<int32_t>(self_row[q0 + i], -1) : -1);
-            t_max = std::max(t_max, in[i + 1] - in[i]);
-        }
-        std::copy(t_row + ent0, t_row + ent0 + pe, in.begin() + 2 * qn + 1);
-        if (hipMemcpyAsync(d_in, in.data(), in.size() * 4, hipMemcpyHostToDevice, dx->stream) != hipSuccess) {
-            set_error("%s: upload of the listed rows failed", who);
-            return MSR_E_HIP;
-        }
-        const int rc = dense_pass_scores(dx, ps, q, q0, qn, d_Q, d_S, e0, true, who);
-        if (rc != MSR_OK) return rc;
-        (void)hipEventRecord(e1, dx->stream);
-        DenseRankArgs ra;
-        ra.S = d_S;
-        ra.ld = dx->n_pad;
-        ra.n = (uint32_t)dx->n;
-        ra.t_ptr = d_in;
-        ra.self_row = reinterpret_cast<const int32_t*>(d_in + qn + 1);
-        ra.t_row = d_in + 2 * qn + 1;
-        ra.out_rank = d_out;
-        ra.out_key = d_out + pe;
-        hipLaunchKernelGGL(dense_rank_rows, dim3(qn, (t_max + kDenseRankGroup - 1) / kDenseRankGroup), dim3(kDenseRankThreads), 0,
-                           dx->stream, ra);
-        HIP_TRY(hipGetLastError());
-        (void)hipEventRecord(e2, dx->stream);
-        const bool c = hipMemcpyAsync(out_rank + ent0, d_out, (size_t)pe * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_key + ent0, d_out + pe, (size_t)pe * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipStreamSynchronize(dx->stream) == hipSuccess;
-        if (!c) {
-            set_error("%s: kernels or result download failed: %s", who, hipGetErrorString(hipGetLastError()));
-            return MSR_E_HIP;
-        }
-        float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, e0, e1);
-        (void)hipEventElapsedTime(&b, e1, e2);
-        t_gemm += a;
-        t_count += b;
-    }
-    if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_count;
-    return MSR_OK;
+    uint32_t pe = 0, t_max = 0;  // the pass's entries, and the most one of its queries lists
+    return lp.run(
+        q, nq, ms, ms ? ms + 1 : nullptr,
+        [&](int q0, uint32_t qn, bool* skip) {
+            const int64_t ent0 = t_ptr[q0];
+            pe = (uint32_t)(t_ptr[q0 + qn] - ent0);
+            if ((*skip = pe == 0)) return (int)MSR_OK;  // nothing listed in this pass: no GEMM either
+            in.assign((size_t)2 * qn + 1 + pe, 0u);
+            t_max = 0;
+            for (uint32_t i = 0; i <= qn; ++i) in[i] = (uint32_t)(t_ptr[q0 + i] - ent0);
+            for (uint32_t i = 0; i < qn; ++i) {
+                in[qn + 1 + i] = (uint32_t)(self_row ? std::max<int32_t>(self_row[q0 + i], -1) : -1);
+                t_max = std::max(t_max, in[i + 1] - in[i]);
+            }
+            std::copy(t_row + ent0, t_row + ent0 + pe, in.begin() + 2 * qn + 1);
+            if (hipMemcpyAsync(d_in, in.data(), in.size() * 4, hipMemcpyHostToDevice, dx->stream) != hipSuccess) {
+                set_error("%s: upload of the listed rows failed", who);
+                return (int)MSR_E_HIP;
+            }
+            return (int)MSR_OK;
+        },
+        [&](int, uint32_t qn, const uint32_t* d_S) {
+            DenseRankArgs ra;
+            ra.S = d_S;
+            ra.ld = dx->n_pad;
+            ra.n = (uint32_t)dx->n;
+            ra.t_ptr = d_in;
+            ra.self_row = reinterpret_cast<const int32_t*>(d_in + qn + 1);
+            ra.t_row = d_in + 2 * qn + 1;
+            ra.out_rank = d_out;
+            ra.out_key = d_out + pe;
+            hipLaunchKernelGGL(dense_rank_rows, dim3(qn, (t_max + kDenseRankGroup - 1) / kDenseRankGroup), dim3(kDenseRankThreads), 0,
+                               dx->stream, ra);
+            HIP_TRY(hipGetLastError());
+            return (int)MSR_OK;
+        },
+        [&](int q0, uint32_t) {
+            const int64_t ent0 = t_ptr[q0];
+            return hipMemcpyAsync(out_rank + ent0, d_out, (size_t)pe * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                   hipMemcpyAsync(out_key + ent0, d_out + pe, (size_t)pe * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess;
+        });
 }
 
-// Deep lists on the dense route: the passes and the GEMM of the search (dense_passes / dense_pass_scores), then
+// Deep lists on the dense route: the pass loop and the GEMM of the search (DensePassLoop), then
 // deep_select_rows (msr_deep_select.hpp, launched through msr_device.hip) over the pass's key rows in the place of
 // select_tiles + merge_lists, for k up to MSR_DEEP_KMAX.
 int msr_dense_search_deep(msr_dense* dx, const void* q, int q_is_f32, int nq, int k, uint32_t* out_idx, uint32_t* out_key,
@@ -608,80 +673,48 @@ int msr_dense_search_deep(msr_dense* dx, const void* q, int q_is_f32, int nq, in
         set_error("%s: bad argument", who);
         return MSR_E_INVAL;
     }
-    if ((q_is_f32 != 0) != dx->f32) {
-        if (dx->f32)
-            set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
-                      "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
-        else
-            set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
-                      "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
-        return MSR_E_INVAL;
-    }
+    if (int rc0 = dense_precision_check(who, dx, q_is_f32)) return rc0;
     if (k < 1 || k > MSR_DEEP_KMAX) {
         set_error("%s: k must be in [1, MSR_DEEP_KMAX = %d] (got %d)", who, MSR_DEEP_KMAX, k);
         return MSR_E_RANGE;
     }
-    if (dx->device < 0) {
-        set_error("%s: the dense handle has no HIP device; there is no CPU dense search path", who);
-        return MSR_E_NODEVICE;
-    }
+    if (int rc0 = dense_device_check(who, dx)) return rc0;
     if (ms) ms[0] = ms[1] = 0.f;
     if (nq == 0) return MSR_OK;
-    HIP_TRY(hipSetDevice(dx->device));
-    const DensePasses ps = dense_passes(dx, nq);
-    const uint32_t qt = ps.qt;
+    DensePassLoop lp(dx, who);
+    if (int rc = lp.begin(nq)) return rc;
+    const uint32_t qt = lp.ps.qt;
     const size_t perq = (size_t)qt * k;
-    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
-    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
     uint32_t* d_idx = (uint32_t*)dx->take(msr_dense::S_DEEP_IDX, perq * 4);
     uint32_t* d_key = (uint32_t*)dx->take(msr_dense::S_DEEP_KEY, perq * 4);
     int32_t* d_n = (int32_t*)dx->take(msr_dense::S_DEEP_N, (size_t)qt * 4);
-    bool ok = d_Q && d_S && d_idx && d_key && d_n;
-    for (hipEvent_t& e : dx->ev)
-        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
-    if (!ok) {
+    if (!lp.ready(d_idx && d_key && d_n)) {
         set_error("device allocation failed in %s (%u queries per pass x %llu docs, k = %d)", who, qt, (unsigned long long)dx->n_pad, k);
         return MSR_E_NOMEM;
     }
-    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
-    double t_gemm = 0, t_sel = 0;
-    for (int q0 = 0; q0 < nq; q0 += (int)qt) {
-        const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
-        int rc = dense_pass_scores(dx, ps, q, q0, qn, d_Q, d_S, e0, true, who);
-        if (rc != MSR_OK) return rc;
-        (void)hipEventRecord(e1, dx->stream);
-        DeepArgs da;
-        da.src = d_S;
-        da.ld = dx->n_pad;
-        da.n = (uint32_t)dx->n;
-        da.rows = qn;
-        da.k = (uint32_t)k;
-        da.out_idx = d_idx;
-        da.out_key = d_key;
-        da.out_f32 = nullptr;
-        da.out_n = d_n;
-        rc = launch_deep_select(dx->stream, da);
-        if (rc != MSR_OK) return rc;
-        (void)hipEventRecord(e2, dx->stream);
-        const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_idx, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_key + (size_t)q0 * k, d_key, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipStreamSynchronize(dx->stream) == hipSuccess;
-        if (!c) {
-            set_error("%s: kernels or result download failed: %s", who, hipGetErrorString(hipGetLastError()));
-            return MSR_E_HIP;
-        }
-        float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, e0, e1);
-        (void)hipEventElapsedTime(&b, e1, e2);
-        t_gemm += a;
-        t_sel += b;
-    }
-    if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_sel;
-    return MSR_OK;
+    return lp.run(
+        q, nq, ms, ms ? ms + 1 : nullptr,
+        [&](int, uint32_t qn, const uint32_t* d_S) {
+            DeepArgs da;
+            da.src = d_S;
+            da.ld = dx->n_pad;
+            da.n = (uint32_t)dx->n;
+            da.rows = qn;
+            da.k = (uint32_t)k;
+            da.out_idx = d_idx;
+            da.out_key = d_key;
+            da.out_f32 = nullptr;
+            da.out_n = d_n;
+            return launch_deep_select(dx->stream, da);
+        },
+        [&](int q0, uint32_t qn) {
+            return hipMemcpyAsync(out_idx + (size_t)q0 * k, d_idx, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                   hipMemcpyAsync(out_key + (size_t)q0 * k, d_key, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
+                   hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess;
+        });
 }
 
-// Filtered search on the dense route: the passes and the GEMM of the search (dense_passes / dense_pass_scores), then
+// Filtered search on the dense route: the pass loop and the GEMM of the search (DensePassLoop), then
 // select_tiles_filtered (msr_filter.hpp, launched through msr_filter.hip) in the place of select_tiles, then the search's
 // merge. The doc sets are uploaded once per call (S_FILTER: bitmap | any | q_set); the kernel indexes q_set by the call's
 // query, the per-tile lists are pass-local.
@@ -694,47 +727,26 @@ int msr_dense_search_filtered(msr_dense* dx, const void* q, int q_is_f32, int nq
         return MSR_E_INVAL;
     }
     if (int rc0 = filter_check_shapes(who, set_bits, n_sets, q_set)) return rc0;
-    if ((q_is_f32 != 0) != dx->f32) {
-        if (dx->f32)
-            set_error("%s: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass f32 queries with "
-                      "q_is_f32 = 1, or open an fp16 handle with msr_dense_open", who);
-        else
-            set_error("%s: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass fp16 queries with "
-                      "q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32", who);
-        return MSR_E_INVAL;
-    }
+    if (int rc0 = dense_precision_check(who, dx, q_is_f32)) return rc0;
     if (k < 1 || k > MSR_KMAX) {
         set_error("%s: k must be in [1, MSR_KMAX = %d] (got %d)", who, MSR_KMAX, k);
         return MSR_E_RANGE;
     }
     if (int rc0 = filter_check_ranges(who, n_sets, q_set, nq)) return rc0;
-    if (dx->device < 0) {
-        set_error("%s: the dense handle has no HIP device; there is no CPU dense search path", who);
-        return MSR_E_NODEVICE;
-    }
+    if (int rc0 = dense_device_check(who, dx)) return rc0;
     if (ms) ms[0] = ms[1] = 0.f;
     if (nq == 0) return MSR_OK;
-    HIP_TRY(hipSetDevice(dx->device));
-    const DensePasses ps = dense_passes(dx, nq);
-    const uint32_t qt = ps.qt;
-    const size_t perq = (size_t)qt * k;
+    DensePassLoop lp(dx, who);
+    if (int rc = lp.begin(nq)) return rc;
     FilterImage fi;
     fi.build(set_bits, n_sets, q_set, nq, dx->n, dx->tile_docs, dx->n_tiles);
     auto al = [](size_t n) { return (n + 63) / 64 * 64; };  // sub-buffers start on 256-byte boundaries (in u32 units)
     const size_t o_bits = 0, o_any = al(fi.bits.size()), o_qs = o_any + al(fi.any.size()), f_words = o_qs + al(fi.q_set.size());
-    uint8_t* d_Q = (uint8_t*)dx->take(msr_dense::S_Q, (size_t)ps.qt_pad * ps.q_row);
-    uint32_t* d_S = (uint32_t*)dx->take(msr_dense::S_S, (size_t)ps.qt_pad * dx->n_pad * 4);
-    uint64_t* d_part = (uint64_t*)dx->take(msr_dense::S_PART, (size_t)dx->n_tiles * perq * 8);
-    uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_ORD, perq * 4);
-    uint32_t* d_su = (uint32_t*)dx->take(msr_dense::S_SU, perq * 4);
-    float* d_sf = (float*)dx->take(msr_dense::S_SF, perq * 4);
-    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_N, (size_t)qt * 4);
+    DenseLists ls{dx, k};
+    const bool own = ls.take(lp.ps.qt);
     uint32_t* d_f = (uint32_t*)dx->take(msr_dense::S_FILTER, f_words * 4);
-    bool ok = d_Q && d_S && d_part && d_ord && d_su && d_sf && d_n && d_f;
-    for (hipEvent_t& e : dx->ev)
-        if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
-    if (!ok) {
-        set_error("device allocation failed in %s (%u queries per pass x %llu docs, %d sets)", who, qt,
+    if (!lp.ready(own && d_f)) {
+        set_error("device allocation failed in %s (%u queries per pass x %llu docs, %d sets)", who, lp.ps.qt,
                   (unsigned long long)dx->n_pad, n_sets);
         return MSR_E_NOMEM;
     }
@@ -750,57 +762,9 @@ int msr_dense_search_filtered(msr_dense* dx, const void* q, int q_is_f32, int nq
     fa.q_set = reinterpret_cast<const int32_t*>(d_f + o_qs);
     fa.stride = fi.stride;
     fa.n_tiles = dx->n_tiles;
-    hipEvent_t e0 = dx->ev[0], e1 = dx->ev[1], e2 = dx->ev[2];
-    double t_gemm = 0, t_sel = 0;
-    for (int q0 = 0; q0 < nq; q0 += (int)qt) {
-        const uint32_t qn = (uint32_t)std::min<int>((int)qt, nq - q0);
-        int rc = dense_pass_scores(dx, ps, q, q0, qn, d_Q, d_S, e0, true, who);
-        if (rc != MSR_OK) return rc;
-        (void)hipEventRecord(e1, dx->stream);
-        SelectArgs se;
-        se.src = d_S;
-        se.part = d_part;
-        se.n_docs = dx->n;
-        se.n_tiles = dx->n_tiles;
-        se.tpr = dx->n_tiles;
-        se.rank = 0;
-        se.nq = qn;
-        se.q0 = (uint32_t)q0;  // the pass's first query in the call: q_set is indexed by q0 + qi, `part` by qi
-        se.qn = qn;
-        se.k = (uint32_t)k;
-        se.unsorted = 0;
-        rc = launch_select_filtered(dx->stream, dx->tile_docs, se, fa);
-        if (rc != MSR_OK) return rc;
-        MergeArgs ma;
-        ma.lists = d_part;
-        ma.list_stride = (uint64_t)qn * k;
-        ma.n_lists = dx->n_tiles;
-        ma.nq = qn;
-        ma.k = (uint32_t)k;
-        ma.out_keys = nullptr;
-        ma.out_ord = d_ord;
-        ma.out_score_u32 = d_su;
-        ma.out_score = d_sf;
-        ma.out_n = d_n;
-        rc = launch_merge(dx->stream, ma);
-        if (rc != MSR_OK) return rc;
-        (void)hipEventRecord(e2, dx->stream);
-        const bool c = hipMemcpyAsync(out_idx + (size_t)q0 * k, d_ord, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_key + (size_t)q0 * k, d_su, (size_t)qn * k * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipMemcpyAsync(out_n + q0, d_n, (size_t)qn * 4, hipMemcpyDeviceToHost, dx->stream) == hipSuccess &&
-                       hipStreamSynchronize(dx->stream) == hipSuccess;
-        if (!c) {
-            set_error("%s: kernels or result download failed: %s", who, hipGetErrorString(hipGetLastError()));
-            return MSR_E_HIP;
-        }
-        float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, e0, e1);
-        (void)hipEventElapsedTime(&b, e1, e2);
-        t_gemm += a;
-        t_sel += b;
-    }
-    if (ms) ms[0] = (float)t_gemm, ms[1] = (float)t_sel;
-    return MSR_OK;
+    return lp.run(q, nq, ms, ms ? ms + 1 : nullptr,
+                  [&](int q0, uint32_t qn, const uint32_t* d_S) { return ls.stage(q0, qn, d_S, false, &fa); },
+                  [&](int q0, uint32_t qn) { return ls.fetch(q0, qn, out_idx, out_key, out_n, hipMemcpyDeviceToHost); });
 }
 
 }  // extern "C"
@@ -2465,15 +2429,7 @@ int msr_hybrid_search_union(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, 
         set_error("msr_hybrid_search_union: bad argument");
         return MSR_E_INVAL;
     }
-    if ((q_is_f32 != 0) != dx->f32) {
-        if (dx->f32)
-            set_error("msr_hybrid_search_union: q_is_f32 = 0 but the dense handle holds f32 rows (msr_dense_open_f32); pass "
-                      "f32 queries with q_is_f32 = 1, or open an fp16 handle with msr_dense_open");
-        else
-            set_error("msr_hybrid_search_union: q_is_f32 = 1 but the dense handle holds fp16 rows (msr_dense_open); pass "
-                      "fp16 queries with q_is_f32 = 0, or open an f32 handle with msr_dense_open_f32");
-        return MSR_E_INVAL;
-    }
+    if (int rc0 = dense_precision_check("msr_hybrid_search_union", dx, q_is_f32)) return rc0;
     if (!ix->dev) {
         set_error("index handle has no HIP device bound; there is no CPU scoring path");
         return MSR_E_NODEVICE;

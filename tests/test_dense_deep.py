@@ -120,6 +120,35 @@ def test_identities_with_search_and_rank_rows(m, precision):
         dix.close()
 
 
+def test_two_passes_at_the_first_k_above_2048():
+    """The pass loop of the dense calls (DensePassLoop, csrc/msr_hybrid.hip) under the deep selection, over more than one
+    pass: a pass's key rows stay at or below 256 MiB, so rb_max = max(1, 2^28 / (n_pad * 4 * 256)) blocks of 256 queries;
+    once n_pad exceeds 2^17 rows that is 1 and 293 queries run as 256 + 37 (tests/test_dense_filtered.py walks the same
+    passes). The queries are 40 distinct dyadic rows drawn by i % 40 (every score exact in any order), so a row lands in
+    both passes; k = 2049 is the first k of the 8192-key instance. Expected: tests/deep_ref.py on the exact keys."""
+    from tests import deep_ref as dr
+    from tests.select_ref import f32_keys as exact_keys
+
+    n, nq, h, k = 16 * 8192 + 37, 293, 8, 2049
+    n_pad = -(-n // 8192) * 8192
+    assert max(1, (256 << 20) // (n_pad * 4 * 256)) == 1 and max(1, (256 << 20) // ((n_pad - 8192) * 4 * 256)) == 2
+    rng = np.random.default_rng(2049)
+    p = dyadic(rng, (n, h))
+    base = dyadic(rng, (40, h))
+    pick = np.arange(nq) % 40
+    assert len(set(pick[:256].tolist()) & set(pick[256:].tolist())) == 37          # rows scored in both passes
+    K = exact_keys((base.astype(np.float64) @ p.astype(np.float64).T + 0.0).astype(np.float32)).astype(np.int64)
+    assert (K > 0).all()
+    want = dr.topk_rows(K, k)                                      # of the 40 distinct queries
+    dix = _open(p, "f32")
+    try:
+        got = dix.search_keys_deep(base[pick], k)
+    finally:
+        dix.close()
+    _assert_equal(got, tuple(w[pick] for w in want))
+    assert (got[2] == k).all()
+
+
 def test_scratch_stays_on_the_handle(m):
     p, q, _ = _f32_case()
     dix = _open(p[:9000], "f32")

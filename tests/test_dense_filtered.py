@@ -196,6 +196,55 @@ def test_two_passes_with_different_q_sets(m):
         assert cnt[i] == w[2] == 100 and (idx[i] == w[0]).all() and (key[i] == w[1]).all(), i
 
 
+def test_calls_interleaved_on_one_handle(m):
+    """search, search_deep, search_filtered and rank_rows share the query and score scratch of the handle (S_Q, S_S), the
+    plain and the filtered search also their list and result slots, and all four one pass loop (csrc/msr_hybrid.hip).
+    Interleaved on one handle each call returns what it returns alone on a fresh handle and what the references give;
+    the first search repeated at the end returns the same again; a second round allocates nothing."""
+    from tests import deep_ref as dr
+    from tests import dense_rank_ref as drr
+
+    c = case("f32")
+    rng = np.random.default_rng(5)
+    q = dyadic(rng, (260, H["f32"]))
+    K = keys_of(q, c["p"])
+    assert (K > 0).all()
+    member = c["member"][[4, 5]]                                             # even, span
+    q_set = (np.arange(7) % 3 - 1).astype(np.int32)
+    t_ptr, t_row = drr.targets_csr(drr.random_targets(rng, 20, N, lo=0, hi=5))
+    calls = [("search", lambda d: d.search_keys(q[:3], 10)),
+             ("search_deep", lambda d: d.search_keys_deep(q, 2049)),
+             ("search_filtered", lambda d: d.search_keys_filtered(q[:7], 100, member, q_set)),
+             ("rank_rows", lambda d: d.rank_rows(q[:20], t_ptr, t_row)),
+             ("search", lambda d: d.search_keys(q[:3], 10))]
+    want = [fr.cut(dr.topk_rows(K[:3], 10), 10), dr.topk_rows(K, 2049), fr.masked_topk(K[:7], member, q_set, 100),
+            drr.ranks_from_keys(K[:20], t_ptr, t_row)]
+    want.append(want[0])
+    alone = []
+    for name, call in calls[:4]:
+        dix = _open(c["p"], "f32")
+        try:
+            alone.append(call(dix))
+        finally:
+            dix.close()
+    alone.append(alone[0])
+    dix = _open(c["p"], "f32")
+    try:
+        first = [call(dix) for name, call in calls]
+        before = dix.stats()
+        second = [call(dix) for name, call in calls]
+        assert dix.stats() == before and before["device_allocs"] > 0
+    finally:
+        dix.close()
+    for (name, _), w, a, r1, r2 in zip(calls, want, alone, first, second):
+        for got in (a, r1, r2):
+            assert len(got) == len(w), name
+            for g, x in zip(got, w):
+                assert g.dtype == x.dtype and g.shape == x.shape and (g == x).all(), name
+    for a, b in zip(first[0], first[4]):
+        assert a.tobytes() == b.tobytes()
+
+
 def test_small_index_one_tile(m):
     """At most 4096 rows: one 4096-row tile (another instance of the kernel)."""
     c = case("f32")

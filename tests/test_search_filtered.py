@@ -191,6 +191,21 @@ def test_staged_route_mixed(case_c):
         compare(c["ix"].search_filtered(*rr.csr(c["rows"]), k, c["member"], q_set), fr.cut(ref, k))
 
 
+def test_staged_route_full_set_is_the_unfiltered_search(case_c):
+    """One full set at the shape where stage 1, its merge and the theta launch all run: msr_search_filtered and
+    msr_search_csr go through the one staged routine (staged_search, csrc/msr_device.hip) with another scorer each, and
+    return bit-equal arrays, which are the reference's."""
+    c = case_c
+    q = rr.csr(c["rows"])
+    full = np.ones((1, NC), dtype=bool)
+    ref = fr.masked_topk(c["S"], full, None, 1000)
+    for k in (10, 1000):
+        got = c["ix"].search_filtered(*q, k, full, None)
+        compare(got, fr.cut(ref, k))
+        for a, b in zip(got, c["ix"].search_csr(*q, k)):                      # bit-equal, padding included
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
 # --------------------------------------------------------------------------------------- identities
 @PATHS
 def test_full_set_is_the_unfiltered_search(case_a, path):

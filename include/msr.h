@@ -524,6 +524,40 @@ int msr_hybrid_search_union(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, 
                             const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
                             int32_t* out_n, uint8_t* out_src, uint32_t* out_sparse_u32, float* out_dense, float* out_range,
                             float ms[4]);
+/* ---- alpha sweep: ONE hybrid scoring fused at many alphas. alpha is the one number the reference's hybrid run is tuned
+ * by (--alpha, weights = [alpha, 1 - alpha], src/search.py:459, fuse(), src/hybrid.py:32-53), and nothing before the last
+ * two fmafs of the FUSION CONTRACT depends on it: the depth lists, their members, their extremes and every t_d / t_s are
+ * the same at every alpha. This call runs the union pass of msr_hybrid_search_union once (sparse scores, GEMM, both
+ * depth selections, the union), keeps its outputs on the device and re-fuses and re-ranks them per alpha (fuse_sweep),
+ * where a sweep over msr_hybrid_search[_f32] pays the whole scoring once per alpha.
+ * Inputs mean what they mean for msr_hybrid_search_union; q_is_f32 must match the handle. alphas: n_alphas floats,
+ * duplicates allowed, values outside [0, 1] not refused (as in msr_hybrid_search), a non-finite one is MSR_E_INVAL.
+ * 1 <= depth <= MSR_KMAX, 1 <= k <= 2 * depth, 1 <= n_alphas <= MSR_SWEEP_MAX_ALPHAS.
+ * Outputs: out_ord / out_score row-major [n_alphas][nq][k], out_n [n_alphas][nq]; padding 0xFFFFFFFF / 0.f.
+ * CONTRACT / IDENTITIES, all bit for bit:
+ *   - slice a = the first k columns of msr_hybrid_search_union at alpha = alphas[a]: ordinals, score bits,
+ *     out_n = min(k, that call's out_n);
+ *   - hence, for k <= MSR_KMAX, slice a = msr_hybrid_search[_f32] at that alpha, depth and k, on whichever of the two
+ *     candidate / fused paths that call takes (both use the lower-ordinal dense tie rule);
+ *   - slice a = tests/fusion_ref.topk(fuse(S, D, depth, alphas[a], self_ord), k);
+ *   - a slice depends neither on which other alphas are in the call nor on their order.
+ * t_s = 1 is decided on the exact u32 sparse maximum of the unfiltered list, which the union pass hands to the sweep
+ * beside out_range's f32 images (a member can share the maximum's image without being the maximum).
+ * ms = {candidate kernel, dense GEMM, 0, the union pass's fusion kernel, the sweep kernel(s) summed, number of alpha
+ * groups launched}: the alphas go in groups whose [group][nq][k] lists fit 256 MiB of device staging (at least one alpha per
+ * group), each group is downloaded before the next is launched.
+ * Supported handles: msr_hybrid_search_union's (whole index, 4096- or 8192-doc tiles, a single-tile index included,
+ * fp16: h % 8 == 0); any other handle is MSR_E_INVAL. The tile quota (MSR_HYBRID_QUOTA) and the second round only affect
+ * the pass before the sweep. Scratch stays on the dense handle and only grows: a repeated call of one shape allocates
+ * nothing (msr_dense_stats).
+ * Argument errors, before any device work, in this order: MSR_E_INVAL (null ix / dx / q_ptr / alphas / row2ord / outputs, a
+ * null q with nq > 0, nq < 0, the precision mismatch, row counts that differ, an unsupported or shard handle, a
+ * non-finite alpha); MSR_E_RANGE (depth, k, n_alphas); MSR_E_NODEVICE. nq == 0 returns MSR_OK without a launch. */
+#define MSR_SWEEP_MAX_ALPHAS 64
+int msr_hybrid_sweep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                     const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas, int n_alphas,
+                     uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord,
+                     uint32_t* out_ord, float* out_score, int32_t* out_n, float ms[6]);
 
 /* ---- encode-side sparsifier: log(1 + relu(logit)) -> top-k -> rint(x * 100) (src/model.py:104, src/encode.py:69-75).
  * logits: row-major [rows][vocab], f32 (is_f16 = 0) or IEEE fp16 (is_f16 = 1). fp16_math = 1 rounds 1 + relu and the

@@ -16,6 +16,7 @@ MSR_OK = 0
 MSR_F_DROP_DF_EQ_N = 1
 MSR_KMAX = 1024
 MSR_UNION_MAX = 2 * MSR_KMAX
+MSR_SWEEP_MAX_ALPHAS = 64
 MSR_DEEP_KMAX = 16384
 MSR_FILTER_MAX_SETS = 65536
 MSR_RANK_MAX_TARGETS = 64
@@ -111,6 +112,7 @@ SYMBOLS = [
     ("msr_hybrid_search_f32", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_hybrid_search_union", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_float, _U32, _VP, _VP, _VP, _VP, _VP, _VP,
                                      _VP, _VP, _VP, _VP]),
+    ("msr_hybrid_sweep", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_sparsify", _I, [_VP, _I, _I, _I, _U32, _I, _I, _VP, _VP, _VP]),
     ("msr_synth_vectors", _I, [_U64, _U32, _U32, C.c_double, _U64, _I, _VP, _VP, _VP]),
     ("msr_last_error", _CP, []),

@@ -6,6 +6,8 @@
            --dataset_name flickr --queries out/query.tsv --qrels out/qrels.csv --save_dir runs/   (search_sparse.sh)
            [--ranks: exact rank of every judged doc at any depth -> recall / MRR / MedR / MeanR, sparse.ranks.tsv]
            [--explain N: per-token query weight x doc weight of the first N hits and the judged docs, sparse.explain.tsv]
+           [--alphas 0,0.1,...,1: hybrid on the GPU, ONE msr_hybrid_sweep call fuses the scoring at every alpha -> one recall line
+            per alpha, fusion.sweep.tsv; --sweep_runs: fusion.alpha_{a}.trec per alpha]
            [--deep: --depth up to 16384 (msr_search_deep; dense-only: msr_dense_search_deep; hybrid: with --host_fusion)]
     python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
@@ -165,12 +167,79 @@ def normalize_rows(q):
     return q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), 1e-12)
 
 
+def parse_alphas(text, alpha):
+    """--alphas `0,0.1,...,1` -> the floats in the order given, --alpha appended when it is not among them (compared as
+    f32, which is what the library fuses with). Raises ValueError with the reason."""
+    import math
+
+    import numpy as np
+
+    from ._cabi import MSR_SWEEP_MAX_ALPHAS
+
+    parts = [x.strip() for x in str(text).split(",")]
+    if not any(parts):
+        raise ValueError("the list is empty")
+    out = []
+    for x in parts:
+        try:
+            v = float(x)
+        except ValueError:
+            raise ValueError(f"{x!r} is not a number") from None
+        if not math.isfinite(v) or abs(v) > float(np.finfo(np.float32).max):   # (the library fuses in f32)
+            raise ValueError(f"{x!r} is not finite")
+        out.append(v)
+    if not any(np.float32(v) == np.float32(alpha) for v in out):
+        out.append(float(alpha))
+    if len(out) > MSR_SWEEP_MAX_ALPHAS:
+        raise ValueError(f"{len(out)} alphas (--alpha included), at most MSR_SWEEP_MAX_ALPHAS = {MSR_SWEEP_MAX_ALPHAS}")
+    return out
+
+
+def _check_sweep_args(a):
+    """The contradictions of `search --alphas`: every one exits with its own message before any index is opened."""
+    from ._cabi import MSR_KMAX
+
+    if getattr(a, "alphas", None) is None:
+        if getattr(a, "sweep_runs", False):
+            sys.exit("search: --sweep_runs writes one run per alpha of --alphas: give --alphas")
+        return
+    if a.sparse_index is None or a.passage_reps is None:
+        sys.exit("search: --alphas sweeps the hybrid search on the GPU: give both --passage_reps and --sparse_index")
+    for flag, on, why in (
+            ("--host_fusion", a.host_fusion, "the sweep is one msr_hybrid_sweep call on the GPU; fuse() on the host has no sweep"),
+            ("--fusion_union", getattr(a, "fusion_union", False), "the sweep keeps the union on the device and returns the best "
+                                                                  "--fusion_k docs per alpha"),
+            ("--deep", getattr(a, "deep", False), f"the sweep holds at most MSR_KMAX = {MSR_KMAX} docs per list"),
+            ("--doc_sets / --query_sets", getattr(a, "doc_sets", None) or getattr(a, "query_sets", None),
+             "the fused GPU hybrid calls take no doc sets"),
+            ("--ranks", getattr(a, "ranks", False), "a fused rank beyond the depth is not defined"),
+            ("--explain", getattr(a, "explain", None) is not None, "--explain is the sparse-only route")):
+        if on:
+            sys.exit(f"search: --alphas does not combine with {flag}: {why}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("search: --alphas runs in one process (no launcher, WORLD_SIZE = 1)")
+    if not 1 <= a.depth <= MSR_KMAX:
+        sys.exit(f"search: --alphas needs --depth in [1, MSR_KMAX = {MSR_KMAX}] (got {a.depth}; it is not clamped under "
+                 "this flag)")
+    try:
+        a.sweep_alphas = parse_alphas(a.alphas, a.alpha)
+    except ValueError as e:
+        sys.exit(f"search: --alphas {a.alphas!r}: {e}")
+    from .index import SparseIndex
+
+    with SparseIndex(_index_path(a.sparse_index), device=-1) as meta:  # host-side metadata only: no GPU work
+        if meta.tile_docs not in (4096, 8192):
+            sys.exit(f"search: --alphas needs an index with 4096- or 8192-doc tiles, {a.sparse_index} has "
+                     f"{meta.tile_docs}: rebuild it with --tile_docs 4096 / 8192")
+
+
 def _check_search_args(a):
     """Argument checks of `search` that need no index and no GPU."""
     from ._cabi import MSR_DEEP_KMAX, MSR_KMAX
 
     if a.sparse_index is None and a.passage_reps is None:
         sys.exit("search: give --sparse_index (sparse or hybrid search) and/or --passage_reps (dense search)")
+    _check_sweep_args(a)
     deep = bool(getattr(a, "deep", False))
     if deep:
         if not 1 <= a.depth <= MSR_DEEP_KMAX:
@@ -323,7 +392,8 @@ def _cmd_search(a):
     elif p_reps is not None and not a.host_fusion:
         # Hybrid on the GPU (the default): this rank's WHOLE query shard in one msr_hybrid_search call — sparse scores,
         # both depth lists, the reference's fusion (src/hybrid.py:32-53) and the top --fusion_k never leave HBM.
-        sparse_run, dense_run, fusion_run = _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts)
+        sweep = {} if getattr(a, "alphas", None) is not None else None
+        sparse_run, dense_run, fusion_run = _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts, sweep)
     else:
         if p_reps is not None:  # --host_fusion: the reference's own structure, batch by batch (src/search.py:455-461)
             from .dense import FaissFlatSearcher
@@ -352,6 +422,9 @@ def _cmd_search(a):
     if a.save_dir:
         os.makedirs(a.save_dir, exist_ok=True)
         sfx = f".rank{rank}" if world > 1 else ""
+        if getattr(a, "sweep_runs", False):
+            for x, run in zip(sweep["alphas"], _sweep_runs(sweep, qids)):
+                write_trec_run(run, os.path.join(a.save_dir, f"fusion.alpha_{x:g}.trec"))
         if not dense_only:  # (dense-only search writes the dense run alone: no sparse.trec, no fusion.trec)
             write_trec_run(sparse_run, os.path.join(a.save_dir, "sparse.trec" + sfx), name="sparse")
         if dense_run or dense_only:
@@ -383,6 +456,8 @@ def _cmd_search(a):
                             os.remove(p)
     if a.qrels:
         ds = ds or CrossModalQrels(a.qrels, a.dataset_name)
+        if getattr(a, "alphas", None) is not None:
+            _report_sweep(a, sweep, ds, qids)
         m = RecallMetrics(ds, dense_run, sparse_run, fusion_run, p_lookup or [], qids, args,
                           denominator=None if (a.compat_denominator or world == 1) else n_queries)
         m.sort_and_count()
@@ -457,6 +532,46 @@ def _filtered_search(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
 
             fusion_run = fuse([dense_run, sparse_run], [a.alpha, 1 - a.alpha])
     return sparse_run, dense_run, fusion_run
+
+
+def _sweep_runs(sweep, qids):
+    """One fused run per alpha of a sweep, in the layout of _hybrid_on_gpu's fusion_run."""
+    table = sweep["table"]
+    for ords, fs, cnt in zip(sweep["ords"], sweep["scores"], sweep["n"]):
+        fs_rows = fs.tolist()
+        yield {qid: dict(zip(table[ords[i, :cnt[i]]].tolist(), fs_rows[i][:cnt[i]])) for i, qid in enumerate(qids)}
+
+
+def _report_sweep(a, sweep, ds, qids):
+    """search --alphas with --qrels: one line per alpha with the fusion recalls RecallMetrics reports for that alpha's
+    lists (recall.sweep_recall: doc ids and targets compared as ints like src/metrices.py:33,41-44, the same denominator)
+    and, with --save_dir, fusion.sweep.tsv: alpha, r@1, r@5, r@10, r@100, r@200, in the order given."""
+    from .recall import RECALL_KS, sweep_recall
+
+    def as_int(x):
+        try:
+            return int(x)
+        except (TypeError, ValueError):
+            return str(x)
+
+    ord_of = {as_int(d): o for o, d in enumerate(sweep["table"].tolist())}
+    targets = []
+    for qid in qids:
+        t = ds.get_target(qid, a.query_type)
+        t = t if isinstance(t, list) else [t]
+        targets.append([ord_of[as_int(x)] for x in t if as_int(x) in ord_of])
+    counts = sweep_recall(sweep["ords"], sweep["n"], targets, RECALL_KS)
+    denom = max(len(qids), 1)
+    rows = []
+    for x, c in zip(sweep["alphas"], counts.tolist()):
+        r = [v / denom for v in c]
+        rows.append((x, r))
+        print("Fusion/Hybrid sweep alpha {:g}: r@1 {}, r@5 {}, r@10 {}, r@100 {}, r@200 {}".format(x, *r))
+    if a.save_dir:
+        os.makedirs(a.save_dir, exist_ok=True)
+        with open(os.path.join(a.save_dir, "fusion.sweep.tsv"), "w") as f:
+            for x, r in rows:
+                f.write("\t".join([f"{x:g}"] + [repr(v) for v in r]) + "\n")
 
 
 def _report_exact_ranks(a, searcher, ds, qids, texts):
@@ -609,19 +724,22 @@ def _report_dense_ranks(a, r):
                         e += 1
 
 
-def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
+def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts, sweep=None):
     """search --passage_reps on the GPU: ONE msr_hybrid_search call for the fused run; the sparse and the dense run the
     reference also reports (src/metrices.py:105-126) come from one whole-shard call each. Returns the three run dicts in
     the reference's layouts (src/search.py:66-82; the fused run without the 'docs' level, src/hybrid.py:32-53).
     --hybrid_f32: an f32 DenseIndex and hybrid_search_f32 (the reference's f32 flat index) instead of fp16.
     --fusion_union: ONE msr_hybrid_search_union call instead, from which all three runs come (fusion.union_to_runs): the
     fused run holds the WHOLE union as the reference's does, and nothing is scored a second time.
+    --alphas (sweep: a dict to fill): ONE msr_hybrid_sweep call (dense.hybrid_sweep) for the whole query file at every alpha
+    of a.sweep_alphas, k = min(--fusion_k, 2 x depth); --alpha's slice is the fused run, so nothing is fused twice, and
+    `sweep` receives every slice (alphas, ords, scores, n, table).
     Difference to --host_fusion: the fused run holds the best --fusion_k docs of the union (the recall reporter reads
     200, src/metrices.py:9), and an exact tie of two DENSE scores at the depth boundary goes to the lower doc ordinal
     instead of the lower row (include/msr.h)."""
     import numpy as np
 
-    from .dense import DenseIndex, hybrid_search, hybrid_search_f32, hybrid_search_union, row_to_ordinal
+    from .dense import DenseIndex, hybrid_search, hybrid_search_f32, hybrid_search_union, hybrid_sweep, row_to_ordinal
     from .fusion import union_to_runs
     from .run import get_run_dict
 
@@ -645,7 +763,15 @@ def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts):
                                                                      self_ord, drop_df_eq_n=drop,
                                                                      with_lists=not a.fusion_only)
             return union_to_runs(qids, table, ords, cnt, fs, src, su, de, rng)
-        ords, fs, cnt, _ = hybrid(ix, dix, q_ptr, q_term, q_w, q, depth, k_f, a.alpha, r2o, self_ord, drop_df_eq_n=drop)
+        if sweep is not None:
+            alphas = list(a.sweep_alphas)
+            s_ords, s_fs, s_cnt, _ = hybrid_sweep(ix, dix, q_ptr, q_term, q_w, q, depth, max(1, min(a.fusion_k, 2 * depth)),
+                                                  alphas, r2o, self_ord, drop_df_eq_n=drop)
+            sweep.update(alphas=alphas, ords=s_ords, scores=s_fs, n=s_cnt, table=table)
+            at = [np.float32(x) == np.float32(a.alpha) for x in alphas].index(True)
+            ords, fs, cnt = s_ords[at], s_fs[at], s_cnt[at]
+        else:
+            ords, fs, cnt, _ = hybrid(ix, dix, q_ptr, q_term, q_w, q, depth, k_f, a.alpha, r2o, self_ord, drop_df_eq_n=drop)
         fs_rows = fs.tolist()
         fusion_run = {qid: dict(zip(table[ords[i, :cnt[i]]].tolist(), fs_rows[i][:cnt[i]])) for i, qid in enumerate(qids)}
         sparse_run, dense_run = {}, {}
@@ -761,6 +887,16 @@ def main(argv=None):
                         "handle; --depth <= 1024, not with --host_fusion, --fusion_k is ignored")
     s.add_argument("--fusion_only", action="store_true", help="hybrid on the GPU: skip the separate sparse and dense runs (with or without --fusion_union; "
                                                                    "the fused run then feeds the recall report only: fusion.trec is written beside a dense run)")
+    s.add_argument("--alphas", default=None, metavar="A,B,...",
+                   help="hybrid on the GPU: sweep the fusion weight, e.g. 0,0.1,0.2,0.3,0.4,0.5,0.6,0.7,0.8,0.9,1 (at most 64 "
+                        "values, --alpha is added if absent): ONE msr_hybrid_sweep call scores the whole query file once and "
+                        "fuses it at every alpha, k = min(--fusion_k, 2 x --depth); with --qrels prints one 'Fusion/Hybrid "
+                        "sweep alpha' line per alpha and writes fusion.sweep.tsv under --save_dir; --alpha's slice is the "
+                        "usual fused run; honours --hybrid_f32, --remove_query, --fusion_only; --depth <= 1024, 4096- or "
+                        "8192-doc tiles; not with --host_fusion, --fusion_union, --deep, --doc_sets / --query_sets, --ranks, "
+                        "--explain or under a launcher")
+    s.add_argument("--sweep_runs", action="store_true",
+                   help="with --alphas and --save_dir: also write fusion.alpha_{a}.trec, the fused run of every alpha")
     s.add_argument("--deep", action="store_true",
                    help="lists beyond 1024: lifts --depth to [1, MSR_DEEP_KMAX = 16384] on the sparse-only route "
                         "(msr_search_deep), the dense-only route (msr_dense_search_deep; fp16 with --use_gpu, else f32) and, "

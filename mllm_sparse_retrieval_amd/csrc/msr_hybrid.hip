@@ -9,6 +9,7 @@
 #include "msr_dense_rank.hpp"
 #include "msr_gemm_f32.hpp"
 #include "msr_gemm_w4.hpp"
+#include "msr_sweep.hpp"
 
 using namespace msr;
 
@@ -133,7 +134,7 @@ struct msr_dense {
     // device scratch of the fused hybrid call (query matrix, score rows, result lists), kept between calls and only ever
     // grown: six hipMalloc / hipFree pairs of up to 200 MB cost a call more than its kernels
     enum Slot { S_Q = 0, S_S, S_ORD, S_SF, S_N, S_SELF, S_CS, S_META, S_FLAGS, S_QLIST, S_PART, S_SU, S_USRC, S_USPARSE, S_UDENSE,
-                S_URANGE, S_RANK_IN, S_RANK_OUT, S_DEEP_IDX, S_DEEP_KEY, S_DEEP_N, S_FILTER, S_COUNT };
+                S_URANGE, S_UEXT, S_SW_ORD, S_SW_SF, S_SW_N, S_RANK_IN, S_RANK_OUT, S_DEEP_IDX, S_DEEP_KEY, S_DEEP_N, S_FILTER, S_COUNT };
     void* scratch[S_COUNT] = {};
     size_t scratch_bytes[S_COUNT] = {};
     uint64_t n_device_allocs = 0;  // hipMalloc calls made on behalf of this handle (steady-state calls make none)
@@ -1571,12 +1572,14 @@ __device__ __forceinline__ uint64_t kth_largest_u64(Each each, uint32_t need, Kt
 // search of its (unique) fused key in the sorted LDS array (<= 11 probes per member, ~2 000 members over 256 or 512
 // threads) — no slot array to carry through the sort, no second sort.
 
-// The four optional outputs of msr_hybrid_search_union on the device (null = not wanted)
+// The optional outputs of the union pass on the device (null = not wanted): the four of msr_hybrid_search_union, and the
+// exact sparse extremes that only msr_hybrid_sweep asks for
 struct UnionOut {
     uint8_t* src;      // [nq][2 x depth] bit 0: in the dense depth list, bit 1: in the sparse depth list
     uint32_t* sparse;  // [nq][2 x depth] exact sparse score where bit 1 is set, else 0
     float* dense;      // [nq][2 x depth] dense score where bit 0 is set, else 0
     float* range;      // [nq][4] {dense max, dense min, sparse max, sparse min} of the unfiltered depth lists
+    uint32_t* ext;     // [nq][2] {sparse max, sparse min} as exact u32 (the f32 images above can hide the maximum)
 };
 
 template <int NT, int EPT /* records per thread held in registers */, bool UNION = false>
@@ -1735,6 +1738,10 @@ __global__ __launch_bounds__(NT) void hybrid_fuse_query(const HybridArgs h, cons
         if (u.range && tid == 0) {
             float* const r = u.range + (uint64_t)q * 4;
             r[0] = dmax, r[1] = dmin, r[2] = smax, r[3] = smin;
+        }
+        if (u.ext && tid == 0) {
+            u.ext[(uint64_t)q * 2] = need_s ? smax_u : 0u;
+            u.ext[(uint64_t)q * 2 + 1] = smin_u;
         }
         if (!(u.src || u.sparse || u.dense)) return;  // (uniform)
         for (uint32_t i = n_out + tid; i < h.k; i += NT) {
@@ -2036,11 +2043,20 @@ static uint32_t tile_quota(uint64_t tile_docs, uint64_t n, uint32_t depth) {
 // repeated with quota = depth. ms = {candidate kernel, dense GEMM, 0, fusion kernel}.
 // un != null (msr_hybrid_search_union): k = 2 x depth is the row length, hybrid_fuse_query<UNION> keeps the whole union and fills
 // the optional arrays that un names (host pointers, null = not wanted: neither allocated, written nor downloaded).
+// un->resident != null (msr_hybrid_sweep): every side array and the exact sparse extremes are computed, NOTHING is downloaded
+// (out_ord / out_score / out_n may be null) and *resident receives the device pointers, which stay valid in the dense
+// handle's scratch until its next call.
+struct UnionResident {
+    UnionOut uo;
+    const uint32_t* ord;  // [nq][2 x depth] members by the fused score of the pass's alpha
+    const int32_t* n;     // [nq]
+};
 struct UnionHost {
     uint8_t* src;
     uint32_t* sparse;
     float* dense;
     float* range;
+    UnionResident* resident = nullptr;
 };
 
 static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term,
@@ -2082,13 +2098,15 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
     uint32_t* d_flags = (uint32_t*)dx->take(msr_dense::S_FLAGS, std::max<size_t>(nq, 1) * 4);
     uint32_t* d_qlist = (uint32_t*)dx->take(msr_dense::S_QLIST, std::max<size_t>(nq, 1) * 4);
     bool ok = s.ok && d_rec && d_meta && d_flags && d_qlist;
-    UnionOut uo = {nullptr, nullptr, nullptr, nullptr};
+    UnionOut uo = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t per_union = std::max<size_t>((size_t)nq * k, 1);  // (un: k = 2 x depth)
+    const bool resident = un && un->resident;
     if (un) {
-        if (un->src) ok = (uo.src = (uint8_t*)dx->take(msr_dense::S_USRC, per_union)) != nullptr && ok;
-        if (un->sparse) ok = (uo.sparse = (uint32_t*)dx->take(msr_dense::S_USPARSE, per_union * 4)) != nullptr && ok;
-        if (un->dense) ok = (uo.dense = (float*)dx->take(msr_dense::S_UDENSE, per_union * 4)) != nullptr && ok;
-        if (un->range) ok = (uo.range = (float*)dx->take(msr_dense::S_URANGE, std::max<size_t>(nq, 1) * 16)) != nullptr && ok;
+        if (resident) ok = (uo.ext = (uint32_t*)dx->take(msr_dense::S_UEXT, std::max<size_t>(nq, 1) * 8)) != nullptr && ok;
+        if (un->src || resident) ok = (uo.src = (uint8_t*)dx->take(msr_dense::S_USRC, per_union)) != nullptr && ok;
+        if (un->sparse || resident) ok = (uo.sparse = (uint32_t*)dx->take(msr_dense::S_USPARSE, per_union * 4)) != nullptr && ok;
+        if (un->dense || resident) ok = (uo.dense = (float*)dx->take(msr_dense::S_UDENSE, per_union * 4)) != nullptr && ok;
+        if (un->range || resident) ok = (uo.range = (float*)dx->take(msr_dense::S_URANGE, std::max<size_t>(nq, 1) * 16)) != nullptr && ok;
     }
     int rc = MSR_OK;
     if (!ok) {
@@ -2225,8 +2243,14 @@ static int hybrid_search_multitile(msr_index* ix, msr_dense* dx, const int64_t* 
             t_cand += c;
             t_fuse += f;
         }
-        rc = hybrid_download(ha, nq, k, out_ord, out_score, out_n);
-        if (rc == MSR_OK && un && nq &&
+        if (resident) {
+            un->resident->uo = uo;
+            un->resident->ord = ha.out_ord;
+            un->resident->n = ha.out_n;
+        } else {
+            rc = hybrid_download(ha, nq, k, out_ord, out_score, out_n);
+        }
+        if (rc == MSR_OK && un && !resident && nq &&
             ((un->src && hipMemcpy(un->src, uo.src, (size_t)nq * k, hipMemcpyDeviceToHost) != hipSuccess) ||
              (un->sparse && hipMemcpy(un->sparse, uo.sparse, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
              (un->dense && hipMemcpy(un->dense, uo.dense, (size_t)nq * k * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
@@ -2463,6 +2487,144 @@ int msr_hybrid_search_union(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, 
     const UnionHost un = {out_src, out_sparse_u32, out_dense, out_range};
     return hybrid_search_multitile(ix, dx, q_ptr, q_term, q_w, q, nq, depth, 2 * depth, alpha, flags, row2ord, self_ord,
                                    out_ord, out_score, out_n, ms, &un);
+}
+
+// Device staging of one fuse_sweep launch's [alphas][nq][k] lists (ordinals + scores): the bound of the deep calls. A
+// launch takes at least one alpha, so a batch whose ONE alpha is larger is staged whole (the union pass's own arrays of
+// that batch are larger still).
+constexpr size_t kSweepStageBytes = 256ull << 20;
+
+int msr_hybrid_sweep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                     const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas, int n_alphas,
+                     uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord,
+                     float* out_score, int32_t* out_n, float ms[6]) {
+    static_assert(MSR_SWEEP_MAX_ALPHAS == kSweepMaxAlphas, "the kernel's alpha array");
+    if (ms)
+        for (int i = 0; i < 6; ++i) ms[i] = 0.f;
+    if (!ix || !dx || !q_ptr || !row2ord || !alphas || !out_ord || !out_score || !out_n || nq < 0 || (nq && !q)) {
+        set_error("msr_hybrid_sweep: bad argument");
+        return MSR_E_INVAL;
+    }
+    if (int rc0 = dense_precision_check("msr_hybrid_sweep", dx, q_is_f32)) return rc0;
+    const IndexHeader* h = ix->host.h;
+    if (dx->n != h->n_docs) {
+        set_error("the dense index holds %llu rows but the sparse index %llu docs", (unsigned long long)dx->n,
+                  (unsigned long long)h->n_docs);
+        return MSR_E_INVAL;
+    }
+    // the handles of msr_hybrid_search_union: the sweep consumes that pass's resident union
+    const char* why = nullptr;
+    if (ix->term_nshards != 0) why = "a term-range shard handle";
+    else if (ix->shard_ntiles != h->n_tiles) why = "a doc-range shard handle";
+    else if (!hybrid_tile(h->tile_docs)) why = "a tile size other than 4096 / 8192 docs";
+    else if (h->n_tiles > kMaxGridY) why = "more tiles than one launch holds";
+    else if (!dx->f32 && dx->h % 8 != 0) why = "an fp16 dense dimension that is not a multiple of 8";
+    if (why) {
+        set_error("msr_hybrid_sweep: %s is not supported (tile_docs %u, %u of %u tiles resident): the sweep needs a "
+                  "whole-index handle with 4096- or 8192-doc tiles", why, h->tile_docs, ix->shard_ntiles, h->n_tiles);
+        return MSR_E_INVAL;
+    }
+    for (int i = 0; i < std::min(n_alphas, (int)MSR_SWEEP_MAX_ALPHAS); ++i)
+        if (!std::isfinite(alphas[i])) {
+            set_error("msr_hybrid_sweep: alphas[%d] is not finite", i);
+            return MSR_E_INVAL;
+        }
+    if (depth < 1 || depth > MSR_KMAX) {
+        set_error("msr_hybrid_sweep: depth must be in [1, %d] (got %d)", MSR_KMAX, depth);
+        return MSR_E_RANGE;
+    }
+    if (k < 1 || k > 2 * depth) {
+        set_error("msr_hybrid_sweep: k must be in [1, 2 x depth = %d] (got %d)", 2 * depth, k);
+        return MSR_E_RANGE;
+    }
+    if (n_alphas < 1 || n_alphas > MSR_SWEEP_MAX_ALPHAS) {
+        set_error("msr_hybrid_sweep: n_alphas must be in [1, %d] (got %d)", MSR_SWEEP_MAX_ALPHAS, n_alphas);
+        return MSR_E_RANGE;
+    }
+    if (!ix->dev) {
+        set_error("index handle has no HIP device bound; there is no CPU scoring path");
+        return MSR_E_NODEVICE;
+    }
+    if (int rc0 = dense_device_check("msr_hybrid_sweep", dx)) return rc0;
+    if (ix->dev->device != dx->device) {
+        set_error("the sparse and the dense index live on different devices");
+        return MSR_E_INVAL;
+    }
+    if (nq == 0) return MSR_OK;
+    // ---- one scoring: the union pass at any alpha; its outputs stay in the dense handle's scratch
+    UnionResident res;
+    const UnionHost un = {nullptr, nullptr, nullptr, nullptr, &res};
+    if (int rc0 = hybrid_search_multitile(ix, dx, q_ptr, q_term, q_w, q, nq, depth, 2 * depth, alphas[0], flags, row2ord,
+                                          self_ord, nullptr, nullptr, nullptr, ms, &un))
+        return rc0;
+    // ---- the sweep: alpha groups whose lists fit the staging bound; a group's [ga][nq][k] output is one contiguous piece
+    // of the caller's [n_alphas][nq][k] arrays
+    DeviceIndex* d = ix->dev;
+    const size_t per_alpha = (size_t)nq * (size_t)k * 8;
+    const uint32_t ga_max = (uint32_t)std::min<size_t>((size_t)n_alphas, std::max<size_t>(1, kSweepStageBytes / per_alpha));
+    const size_t stage = (size_t)ga_max * (size_t)nq * (size_t)k;
+    uint32_t* d_ord = (uint32_t*)dx->take(msr_dense::S_SW_ORD, stage * 4);
+    float* d_sf = (float*)dx->take(msr_dense::S_SW_SF, stage * 4);
+    int32_t* d_n = (int32_t*)dx->take(msr_dense::S_SW_N, (size_t)ga_max * (size_t)nq * 4);
+    hipEvent_t e0 = d->borrow_event(), e1 = d->borrow_event();
+    int rc = MSR_OK;
+    if (!d_ord || !d_sf || !d_n || !e0 || !e1) {
+        set_error("device allocation failed in msr_hybrid_sweep (%zu staged entries)", stage);
+        rc = MSR_E_NOMEM;
+    }
+    SweepArgs sw;
+    sw.u_ord = res.ord;
+    sw.u_n = res.n;
+    sw.src = res.uo.src;
+    sw.sparse = res.uo.sparse;
+    sw.dense = res.uo.dense;
+    sw.range = res.uo.range;
+    sw.ext = res.uo.ext;
+    sw.w = 2 * (uint32_t)depth;
+    sw.k = (uint32_t)k;
+    sw.out_ord = d_ord;
+    sw.out_score = d_sf;
+    sw.out_n = d_n;
+    sw.nq = (uint32_t)nq;
+    float t_sweep = 0.f;
+    uint32_t groups = 0;
+    for (uint32_t a0 = 0; a0 < (uint32_t)n_alphas && rc == MSR_OK; a0 += ga_max, ++groups) {
+        const uint32_t ga = std::min<uint32_t>(ga_max, (uint32_t)n_alphas - a0);
+        for (int i = 0; i < kSweepMaxAlphas; ++i) sw.alpha[i] = (uint32_t)i < ga ? alphas[a0 + i] : 0.f;
+        sw.n_alphas = ga;
+        (void)hipEventRecord(e0, d->stream);
+        hipLaunchKernelGGL(fuse_sweep, dim3((uint32_t)nq, (ga + kSweepAlphasPerWg - 1) / kSweepAlphasPerWg), dim3(kSweepThreads),
+                           0, d->stream, sw);
+        if (hipGetLastError() != hipSuccess) {
+            set_error("fuse_sweep launch failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = MSR_E_HIP;
+            break;
+        }
+        (void)hipEventRecord(e1, d->stream);
+        if (hipStreamSynchronize(d->stream) != hipSuccess) {
+            set_error("fuse_sweep failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = MSR_E_HIP;
+            break;
+        }
+        const size_t at = (size_t)a0 * nq, rows = (size_t)ga * nq;
+        if (hipMemcpy(out_ord + at * k, d_ord, rows * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_score + at * k, d_sf, rows * k * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_n + at, d_n, rows * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("download failed in msr_hybrid_sweep");
+            rc = MSR_E_HIP;
+            break;
+        }
+        float t = 0.f;
+        (void)hipEventElapsedTime(&t, e0, e1);
+        t_sweep += t;
+    }
+    if (e0) d->return_event(e0);
+    if (e1) d->return_event(e1);
+    if (ms) {
+        ms[4] = t_sweep;
+        ms[5] = (float)groups;
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -374,3 +374,52 @@ def hybrid_search_union(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, d
                                         MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so), ptr(ords), ptr(sc),
                                         ptr(n), ptr(src), ptr(su), ptr(de), ptr(rng), ms))
     return ords, sc, n, src, su, de, rng, dict(sparse=ms[0], dense_gemm=ms[1], dense_select=ms[2], fusion=ms[3])
+
+
+def hybrid_sweep(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k, alphas, row2ord, self_ord=None,
+                 drop_df_eq_n=True):
+    """ONE hybrid scoring fused at every alpha of `alphas` (msr_hybrid_sweep): the union pass of hybrid_search_union runs
+    once, its union stays on the device and is re-fused and re-ranked per alpha. Slice a is, bit for bit, the first k
+    columns of hybrid_search_union(alpha=alphas[a]) and, for k <= MSR_KMAX, hybrid_search[_f32](alphas[a], k).
+    fp16 or f32 follows dense_index.precision. 1 <= k <= 2 * depth, 1 <= len(alphas) <= MSR_SWEEP_MAX_ALPHAS, finite.
+    -> (doc ordinals uint32 [A, nq, k], fused scores float32 [A, nq, k], n int32 [A, nq], kernel ms per stage: sparse,
+        dense_gemm, dense_select, fusion (the union pass), sweep (the sweep kernels summed), groups (alpha groups launched))."""
+    from . import _cabi
+    from ._cabi import MSR_F_DROP_DF_EQ_N, MSR_SWEEP_MAX_ALPHAS
+
+    f32 = getattr(dense_index, "precision", "fp16") == "f32"
+    al = np.ascontiguousarray(alphas, dtype=np.float32)
+    if al.ndim != 1 or not 1 <= al.size <= MSR_SWEEP_MAX_ALPHAS:
+        raise ValueError(f"alphas needs 1 to MSR_SWEEP_MAX_ALPHAS = {MSR_SWEEP_MAX_ALPHAS} values in one dimension, got "
+                         f"shape {al.shape}")
+    if not np.isfinite(al).all():
+        raise ValueError(f"alphas must be finite, got {al.tolist()}")
+    depth, k = int(depth), int(k)
+    if not 1 <= depth <= MSR_KMAX:
+        raise ValueError(f"depth must be in [1, MSR_KMAX = {MSR_KMAX}], got {depth}")
+    if not 1 <= k <= 2 * depth:
+        raise ValueError(f"k must be in [1, 2 * depth = {2 * depth}], got {k}")
+    if f32:
+        q = _as_f32_rows(q_reps, dense_index.dim)
+    else:
+        q = _as_fp16_rows(q_reps, dense_index.dim, dense_index).view(np.uint16)   # (consumed by the synchronous call below)
+    q_ptr, q_term, q_w = _cabi.as_csr(q_ptr, q_term, q_w)
+    nq = len(q_ptr) - 1
+    if q.shape[0] != nq:
+        raise ValueError("sparse and dense query counts differ")
+    row2ord = np.ascontiguousarray(row2ord, dtype=np.uint32)
+    if row2ord.shape != (dense_index.n,):
+        raise ValueError(f"row2ord needs one ordinal per dense row ({dense_index.n}), got shape {row2ord.shape}")
+    so = None if self_ord is None else np.ascontiguousarray(self_ord, dtype=np.int32)
+    if so is not None and so.shape != (nq,):
+        raise ValueError(f"self_ord needs one entry per query ({nq}), got shape {so.shape}")
+    ords = np.empty((al.size, nq, k), dtype=np.uint32)
+    sc = np.empty((al.size, nq, k), dtype=np.float32)
+    n = np.zeros((al.size, nq), dtype=np.int32)
+    ms = (C.c_float * 6)()
+    check(lib().msr_hybrid_sweep(sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w), ptr(q),
+                                 1 if f32 else 0, nq, depth, k, ptr(al), int(al.size),
+                                 MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so), ptr(ords), ptr(sc),
+                                 ptr(n), ms))
+    return ords, sc, n, dict(sparse=ms[0], dense_gemm=ms[1], dense_select=ms[2], fusion=ms[3], sweep=ms[4],
+                             groups=int(ms[5]))

@@ -146,3 +146,31 @@ def replay_ranks(dataset, dense_run, sparse_run, fusion_run, look_up, query_ids,
     # runs that are empty on rank 0 but not overall still print
     first.dense_run, first.sparse_run, first.fusion_run = dense_run, sparse_run, fusion_run
     return first
+
+
+def sweep_recall(ords, n, targets_by_query, ks=RECALL_KS):
+    """Hit counts of an alpha sweep's lists (dense.hybrid_sweep): ords uint32 [A, nq, k] doc ORDINALS best first,
+    n [A, nq] the valid columns of each row, targets_by_query one iterable of target ordinals per query
+    (CrossModalQrels.get_target through the docid table; a target the index does not hold is left out by the caller).
+    -> int64 [A, len(ks)]: the queries with any target among their first min(k, n) columns. Dividing by the query count
+    gives RecallMetrics' fusion recalls for the same lists (a query without docs counts in the denominator only)."""
+    import numpy as np
+
+    ords = np.asarray(ords)
+    n = np.asarray(n)
+    n_a, nq, width = ords.shape
+    if n.shape != (n_a, nq) or len(targets_by_query) != nq:
+        raise ValueError(f"sweep_recall: ords {ords.shape} needs n of shape {(n_a, nq)} and {nq} target lists, got "
+                         f"{n.shape} and {len(targets_by_query)}")
+    tg = [np.unique(np.asarray(list(t), dtype=np.int64)) for t in targets_by_query]
+    t_max = max((len(t) for t in tg), default=0)
+    # the first column at which a query is hit (width = never), then one comparison per k
+    first = np.full((n_a, nq), width, dtype=np.int64)
+    col = np.arange(width, dtype=np.int64)
+    valid = col[None, None, :] < n[:, :, None]
+    o64 = ords.astype(np.int64)
+    for j in range(t_max):
+        t_j = np.asarray([t[j] if j < len(t) else -1 for t in tg], dtype=np.int64)
+        hit = (o64 == t_j[None, :, None]) & valid
+        first = np.minimum(first, np.where(hit.any(axis=2), hit.argmax(axis=2), width))
+    return np.stack([(first < min(int(k), width)).sum(axis=1) for k in ks], axis=1).astype(np.int64)

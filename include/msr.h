@@ -612,6 +612,48 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
                     uint32_t* out_dense_ord, float* out_dense, int32_t* out_dense_n,
                     float* out_range, float ms[6]);
 
+/* ---- filtered deep hybrid search: msr_hybrid_deep among the docs of each query's set. The doc sets are exactly those of
+ * msr_search_filtered: set_bits is [n_sets][(n_docs + 31) / 32], bitmaps over doc ORDINALS (bits at or above n_docs are
+ * ignored); q_set[i] in [-1, n_sets), -1 = unfiltered; q_set may be NULL when n_sets is 0 (nothing filtered) or 1 (every
+ * query uses set 0); at most MSR_FILTER_MAX_SETS sets. One bitmap serves both sides: the hybrid GEMM runs on the
+ * ordinal-ordered rows. Every other input and every output is msr_hybrid_deep's.
+ * CONTRACT, for query i with set M (all docs when unfiltered): the sparse depth list is the exact top-depth of
+ * {d in M : s(d) > 0}; the dense depth list is the exact top-depth of M (every member is a hit, ties go to the lower
+ * ordinal); the extremes and out_range are those of these two lists, with self_ord still in them when it is a member;
+ * everything after that is the FUSION CONTRACT and msr_hybrid_deep's contract word for word (members, out_members,
+ * out_src, padding, the k cut, the -0 caveat). A self_ord outside M changes nothing. The result is what an index that
+ * holds only M's docs would give.
+ * How: both score rows of msr_hybrid_deep are masked by the set (score_dump_filtered writes a masked sparse row,
+ * mask_key_rows zeroes the dense keys of the non-members) and a key of 0 is "not a member" to every step after that, so
+ * both depth selections, fuse_rows, the fused selection and the source gather run unchanged. A pass without a filtered
+ * query issues exactly msr_hybrid_deep's launches.
+ * IDENTITIES, all bit for bit:
+ *   (a) a full set, q_set[i] = -1 or n_sets = 0 gives row i of msr_hybrid_deep on the same inputs in every output, per
+ *       query in a batch that mixes filtered and unfiltered queries;
+ *   (b) for any set, row i equals tests/fusion_ref.fuse run on the sub-corpus of M's columns (S and D restricted to M,
+ *       self_ord moved to its position in M or to -1, ordinals mapped back): tests/hybrid_filter_ref.py;
+ *   (c) the sparse depth list equals msr_search_filtered at k = depth for depth <= MSR_KMAX, and msr_search_deep with the
+ *       non-members struck out for larger depths;
+ *   (d) an empty set, or a set with no doc at all, gives out_n = 0, out_members = 0, out_range = {0, 0, 0, 0}, empty
+ *       depth lists and padding everywhere;
+ *   (e) a slice depends neither on the other alphas nor on the sets of the other queries.
+ * Handles, passes and scratch are msr_hybrid_deep's (whole-index handles, all five tile sizes, fp16 and f32 dense handles;
+ * the scratch stays on the dense handle and only grows); the set image travels with the call's own upload.
+ * ms = msr_hybrid_deep's six slots (the filtered dump is timed in slot 0), then ms[6] = mask_key_rows summed over the
+ * passes, 0 when no query is filtered.
+ * Argument errors, before any device work, in this order: MSR_E_INVAL (msr_hybrid_deep's, then n_sets < 0, a null
+ * set_bits with n_sets > 0, a null q_set with n_sets > 1); MSR_E_RANGE (depth, k, n_alphas, then n_sets >
+ * MSR_FILTER_MAX_SETS and a q_set entry outside [-1, n_sets)); MSR_E_NODEVICE. nq == 0 returns MSR_OK without a launch. */
+int msr_hybrid_deep_filtered(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                             const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas, int n_alphas,
+                             uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord,
+                             const uint32_t* set_bits, int n_sets, const int32_t* q_set,
+                             uint32_t* out_ord, float* out_score, int32_t* out_n, uint32_t* out_members, /* fused */
+                             uint8_t* out_src,
+                             uint32_t* out_sparse_ord, uint32_t* out_sparse_u32, int32_t* out_sparse_n, /* depth lists, nullable */
+                             uint32_t* out_dense_ord, float* out_dense, int32_t* out_dense_n,
+                             float* out_range, float ms[7]);
+
 /* ---- encode-side sparsifier: log(1 + relu(logit)) -> top-k -> rint(x * 100) (src/model.py:104, src/encode.py:69-75).
  * logits: row-major [rows][vocab], f32 (is_f16 = 0) or IEEE fp16 (is_f16 = 1). fp16_math = 1 rounds 1 + relu and the
  * log to half like a model running in fp16. Outputs [rows][k]: vocabulary ids (ties: lower id first), the selected

@@ -115,6 +115,8 @@ SYMBOLS = [
     ("msr_hybrid_sweep", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_hybrid_deep", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                              _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("msr_hybrid_deep_filtered", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _U32, _VP, _VP, _VP, _I, _VP, _VP,
+                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("msr_sparsify", _I, [_VP, _I, _I, _I, _U32, _I, _I, _VP, _VP, _VP]),
     ("msr_synth_vectors", _I, [_U64, _U32, _U32, C.c_double, _U64, _I, _VP, _VP, _VP]),
     ("msr_last_error", _CP, []),

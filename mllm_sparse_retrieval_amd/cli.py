@@ -11,6 +11,8 @@
            [--deep: --depth up to 16384 (msr_search_deep; dense-only: msr_dense_search_deep; hybrid: with --host_fusion)]
            [--fusion_deep: hybrid on the GPU at --depth up to 16384, ONE msr_hybrid_deep call -> sparse.trec, dense.trec and
             the whole fused union in fusion.trec; with --alphas the sweep outputs]
+           [--fusion_filtered --doc_sets F --query_sets F: --fusion_deep among the docs of each query's set, ONE
+            msr_hybrid_deep_filtered call, the same outputs]
     python -m mllm_sparse_retrieval_amd search --passage_reps dense/ --depth 10 --remove_query \\
            --qrels out/qrels.csv --save_dir runs/                                                  (search_dense.sh)
            [--ranks: exact rank of every judged row at any depth (msr_dense_rank_rows) -> the same metrics, dense.ranks.tsv]
@@ -207,7 +209,8 @@ def _check_sweep_args(a):
         return
     if a.sparse_index is None or a.passage_reps is None:
         sys.exit("search: --alphas sweeps the hybrid search on the GPU: give both --passage_reps and --sparse_index")
-    if getattr(a, "fusion_deep", False):  # (its own contradictions are _check_fusion_deep_args'; no depth or tile limit)
+    # (their own contradictions are _check_fusion_deep_args' / _check_fusion_filtered_args'; no depth or tile limit)
+    if getattr(a, "fusion_deep", False) or getattr(a, "fusion_filtered", False):
         try:
             a.sweep_alphas = parse_alphas(a.alphas, a.alpha)
         except ValueError as e:
@@ -219,7 +222,7 @@ def _check_sweep_args(a):
                                                                   "--fusion_k docs per alpha"),
             ("--deep", getattr(a, "deep", False), f"the sweep holds at most MSR_KMAX = {MSR_KMAX} docs per list"),
             ("--doc_sets / --query_sets", getattr(a, "doc_sets", None) or getattr(a, "query_sets", None),
-             "the fused GPU hybrid calls take no doc sets"),
+             "msr_hybrid_sweep takes no doc sets (the filtered sweep is --fusion_filtered --alphas)"),
             ("--ranks", getattr(a, "ranks", False), "a fused rank beyond the depth is not defined"),
             ("--explain", getattr(a, "explain", None) is not None, "--explain is the sparse-only route")):
         if on:
@@ -258,7 +261,7 @@ def _check_fusion_deep_args(a):
             ("--deep", getattr(a, "deep", False), "--deep is the sparse-only, dense-only and --host_fusion routes; "
                                                   "--fusion_deep takes --depth up to 16384 by itself"),
             ("--doc_sets / --query_sets", getattr(a, "doc_sets", None) or getattr(a, "query_sets", None),
-             "filtered deep hybrid search is not served"),
+             "filtered deep hybrid search is --fusion_filtered (one msr_hybrid_deep_filtered call)"),
             ("--ranks", getattr(a, "ranks", False), "a fused rank beyond the depth is not defined"),
             ("--explain", getattr(a, "explain", None) is not None, "--explain is the sparse-only route")):
         if on:
@@ -274,12 +277,49 @@ def _check_fusion_deep_args(a):
               f"{MSR_DEEP_KMAX} docs and the run reports how many queries were cut", file=sys.stderr)
 
 
+def _check_fusion_filtered_args(a):
+    """The contradictions of `search --fusion_filtered`: every one exits with its own message before any index is opened;
+    the warning about a union that may be cut goes to stderr."""
+    from ._cabi import MSR_DEEP_KMAX
+
+    if not getattr(a, "fusion_filtered", False):
+        return
+    if a.sparse_index is None or a.passage_reps is None:
+        sys.exit("search: --fusion_filtered is the filtered hybrid search on the GPU: give both --passage_reps and "
+                 "--sparse_index")
+    if not (getattr(a, "doc_sets", None) and getattr(a, "query_sets", None)):
+        sys.exit("search: --fusion_filtered needs both --doc_sets FILE (docid<TAB>set) and --query_sets FILE (qid<TAB>set)")
+    for flag, on, why in (
+            ("--host_fusion", a.host_fusion, "--fusion_filtered is one msr_hybrid_deep_filtered call on the GPU, "
+                                             "--host_fusion two filtered lists and fuse() on the host"),
+            ("--fusion_union", getattr(a, "fusion_union", False), "--fusion_filtered returns the whole union itself; "
+                                                                  "msr_hybrid_search_union takes no doc sets"),
+            ("--fusion_deep", getattr(a, "fusion_deep", False), "--fusion_deep is the unfiltered call (msr_hybrid_deep); "
+                                                                "--fusion_filtered alone takes --depth up to 16384"),
+            ("--deep", getattr(a, "deep", False), "--deep is the sparse-only, dense-only and --host_fusion routes; "
+                                                  "--fusion_filtered takes --depth up to 16384 by itself"),
+            ("--ranks", getattr(a, "ranks", False), "a fused rank beyond the depth is not defined"),
+            ("--explain", getattr(a, "explain", None) is not None, "--explain is the sparse-only route")):
+        if on:
+            sys.exit(f"search: --fusion_filtered does not combine with {flag}: {why}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("search: --fusion_filtered runs in one process (no launcher, WORLD_SIZE = 1)")
+    if not 1 <= a.depth <= MSR_DEEP_KMAX:
+        sys.exit(f"search: --fusion_filtered needs --depth in [1, MSR_DEEP_KMAX = {MSR_DEEP_KMAX}] (got {a.depth}; it is "
+                 "not clamped under this flag)")
+    if 2 * a.depth > MSR_DEEP_KMAX:
+        print(f"search: WARNING: --fusion_filtered --depth {a.depth}: a fused union can hold 2 x depth = {2 * a.depth} docs, "
+              f"fusion.trec at most MSR_DEEP_KMAX = {MSR_DEEP_KMAX} per query; a larger union is cut after its best "
+              f"{MSR_DEEP_KMAX} docs and the run reports how many queries were cut", file=sys.stderr)
+
+
 def _check_search_args(a):
     """Argument checks of `search` that need no index and no GPU."""
     from ._cabi import MSR_DEEP_KMAX, MSR_KMAX
 
     if a.sparse_index is None and a.passage_reps is None:
         sys.exit("search: give --sparse_index (sparse or hybrid search) and/or --passage_reps (dense search)")
+    _check_fusion_filtered_args(a)
     _check_fusion_deep_args(a)
     _check_sweep_args(a)
     deep = bool(getattr(a, "deep", False))
@@ -315,7 +355,7 @@ def _check_search_args(a):
                      f"(got {a.explain})")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("search: --explain runs in one process (no launcher, WORLD_SIZE = 1)")
-    if getattr(a, "doc_sets", None) or getattr(a, "query_sets", None):
+    if (getattr(a, "doc_sets", None) or getattr(a, "query_sets", None)) and not getattr(a, "fusion_filtered", False):
         if not (a.doc_sets and a.query_sets):
             sys.exit("search: filtered search needs both --doc_sets FILE (docid<TAB>set) and --query_sets FILE (qid<TAB>set)")
         if deep or getattr(a, "ranks", False) or getattr(a, "explain", None) is not None:
@@ -323,7 +363,8 @@ def _check_search_args(a):
                      "lists and filtered ranks are not served (filter a --deep run on the host instead)")
         if a.sparse_index is not None and a.passage_reps is not None and not a.host_fusion:
             sys.exit("search: filtered hybrid search needs --host_fusion (two filtered lists per query and the reference's "
-                     "fuse() on the host); the fused GPU hybrid calls take no doc sets")
+                     "fuse() on the host, --depth <= 1024) or --fusion_filtered (one msr_hybrid_deep_filtered call on the "
+                     "GPU, --depth up to 16384, --alphas); the other fused GPU hybrid calls take no doc sets")
         if getattr(a, "fusion_union", False):
             sys.exit("search: --doc_sets / --query_sets do not combine with --fusion_union (a fused GPU hybrid call)")
         if not 1 <= a.depth <= MSR_KMAX:
@@ -427,7 +468,12 @@ def _cmd_search(a):
         ds = CrossModalQrels(a.qrels, a.dataset_name)
     t0 = time.time()
     filtered = bool(getattr(a, "doc_sets", None))
-    if filtered:  # sparse-only, dense-only or --host_fusion: one filtered call per side over the whole query file
+    sweep = None
+    if getattr(a, "fusion_filtered", False):  # ONE msr_hybrid_deep_filtered call over the whole query file
+        sweep = {} if getattr(a, "alphas", None) is not None else None
+        sparse_run, dense_run, fusion_run = _hybrid_deep_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts, sweep,
+                                                                filtered=True)
+    elif filtered:  # sparse-only, dense-only or --host_fusion: one filtered call per side over the whole query file
         sparse_run, dense_run, fusion_run = _filtered_search(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts)
     elif dense_only:
         dense_run, dense_ranks = _dense_only_search(a, p_reps, p_lookup, q_reps_by_id, qids, ds)
@@ -831,7 +877,36 @@ def _hybrid_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts, swe
     return sparse_run, dense_run, fusion_run
 
 
-def _hybrid_deep_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts, sweep=None):
+def _ordinal_doc_sets(a, ord_of, qids, n_docs):
+    """--doc_sets / --query_sets as msr_hybrid_deep_filtered takes them: (packed sets over doc ordinals, q_set int32 [nq]).
+    Doc ids map to ordinals as on the filtered sparse route: a doc id the index does not hold and a set name --doc_sets does
+    not define are errors, a query without a line is unfiltered (-1), a doc listed in no set belongs to no set."""
+    import numpy as np
+
+    from .filters import read_doc_sets, read_query_sets, sets_from_ordinals
+
+    doc_sets, query_set = read_doc_sets(a.doc_sets), read_query_sets(a.query_sets)
+    names = list(doc_sets)
+    col = {name: s for s, name in enumerate(names)}
+    lists = []
+    for name in names:
+        unknown = [str(d) for d in doc_sets[name] if str(d) not in ord_of]
+        if unknown:
+            sys.exit(f"search: {a.doc_sets}: doc set {name!r}: the index does not hold doc id {unknown[0]!r}"
+                     + (f" (and {len(unknown) - 1} more)" if len(unknown) > 1 else ""))
+        lists.append([ord_of[str(d)] for d in doc_sets[name]])
+    q_set = np.full(len(qids), -1, dtype=np.int32)
+    for i, qid in enumerate(qids):
+        name = query_set.get(qid)
+        if name is None:
+            continue
+        if name not in col:
+            sys.exit(f"search: query {qid} names doc set {name!r}, which {a.doc_sets} does not define")
+        q_set[i] = col[name]
+    return sets_from_ordinals(lists, n_docs), q_set
+
+
+def _hybrid_deep_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts, sweep=None, filtered=False):
     """search --fusion_deep: ONE msr_hybrid_deep call (dense.hybrid_deep) over the whole query file, --depth up to
     MSR_DEEP_KMAX. All three runs come from it: both depth lists as get_run_dict builds them (min / max over the unfiltered
     list, the query's own doc skipped under --remove_query) and the WHOLE fused union at --alpha, up to
@@ -839,11 +914,13 @@ def _hybrid_deep_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts
     call fuses at every alpha of a.sweep_alphas and `sweep` receives every slice, as on the msr_hybrid_sweep route.
     --hybrid_f32: an f32 DenseIndex instead of fp16. Prints how many queries' unions were cut at k (out_members).
     A dense tie AT the depth boundary goes to the lower doc ordinal (include/msr.h), not to the lower row as --host_fusion's;
-    inside the written dense list, docs of equal score stand by row as there."""
+    inside the written dense list, docs of equal score stand by row as there.
+    search --fusion_filtered (filtered=True): ONE msr_hybrid_deep_filtered call (dense.hybrid_deep_filtered) instead, with the
+    doc sets of --doc_sets / --query_sets over doc ordinals; everything else, the outputs included, is the same."""
     import numpy as np
 
     from ._cabi import MSR_DEEP_KMAX
-    from .dense import DenseIndex, hybrid_deep
+    from .dense import DenseIndex, hybrid_deep, hybrid_deep_filtered
     from .run import get_run_dict
 
     ix = searcher.index
@@ -860,8 +937,13 @@ def _hybrid_deep_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts
         self_ord = np.asarray([ord_of.get(x, -1) for x in qids], dtype=np.int32) if a.remove_query else None
         drop = searcher.min_idf >= 0 if searcher.drop_df_eq_n is None else bool(searcher.drop_df_eq_n)
         alphas = list(a.sweep_alphas) if sweep is not None else [a.alpha]
-        res = hybrid_deep(ix, dix, q_ptr, q_term, q_w, q, depth, k, alphas, r2o, self_ord, drop_df_eq_n=drop,
-                          with_lists=not a.fusion_only)
+        if filtered:
+            bits, q_set = _ordinal_doc_sets(a, ord_of, qids, ix.n_docs)
+            res = hybrid_deep_filtered(ix, dix, q_ptr, q_term, q_w, q, depth, k, alphas, r2o, bits, q_set, self_ord,
+                                       drop_df_eq_n=drop, with_lists=not a.fusion_only)
+        else:
+            res = hybrid_deep(ix, dix, q_ptr, q_term, q_w, q, depth, k, alphas, r2o, self_ord, drop_df_eq_n=drop,
+                              with_lists=not a.fusion_only)
     finally:
         dix.close()
     if sweep is not None:
@@ -871,7 +953,7 @@ def _hybrid_deep_on_gpu(a, searcher, p_reps, p_lookup, q_reps_by_id, qids, texts
     fusion_run = {qid: dict(zip(table[ords[i, :cnt[i]]].tolist(), fs_rows[i][:cnt[i]])) for i, qid in enumerate(qids)}
     cut = int((res.members > cnt.astype(np.int64)).sum())
     if cut or not a.quiet:
-        print(f"search: --fusion_deep: {cut} of {len(qids)} queries have a fused union of more than k = {k} docs (cut after "
+        print(f"search: --fusion_{'filtered' if filtered else 'deep'}: {cut} of {len(qids)} queries have a fused union of more than k = {k} docs (cut after "
               f"the best {k}); largest union {int(res.members.max(initial=0))} docs")
     sparse_run, dense_run = {}, {}
     if not a.fusion_only:
@@ -1015,12 +1097,21 @@ def main(argv=None):
                         "unions were cut (possible when 2 x --depth > 16384: a warning says so); with --alphas the same "
                         "call fuses at every alpha (fusion.sweep.tsv, --sweep_runs: fusion.alpha_{a}.trec); needs "
                         "--passage_reps and --sparse_index; honours --hybrid_f32, --use_gpu, --remove_query, --fusion_only; "
-                        "not with --host_fusion, --fusion_union, --deep, --doc_sets / --query_sets, --ranks, --explain or "
-                        "under a launcher")
+                        "not with --host_fusion, --fusion_union, --deep, --doc_sets / --query_sets (that is "
+                        "--fusion_filtered), --ranks, --explain or under a launcher")
+    s.add_argument("--fusion_filtered", action="store_true",
+                   help="filtered hybrid on the GPU: --fusion_deep among the docs of each query's set, ONE "
+                        "msr_hybrid_deep_filtered call over the whole query file; needs --doc_sets FILE --query_sets FILE, "
+                        "--passage_reps and --sparse_index; --depth in [1, 16384], not clamped (a warning when 2 x --depth > "
+                        "16384); writes what --fusion_deep writes; works with --alphas and --sweep_runs, --hybrid_f32, "
+                        "--use_gpu, --remove_query, --fusion_only; not with --host_fusion, --fusion_union, --fusion_deep, "
+                        "--deep, --ranks, --explain or under a launcher")
     s.add_argument("--doc_sets", default=None, metavar="FILE",
                    help="filtered search: TSV lines docid<TAB>set naming doc sets; with --query_sets every query searches "
                         "only the docs of its set (msr_search_filtered / msr_dense_search_filtered): sparse-only, dense-only "
-                        "and --host_fusion routes; refused on the GPU-fused hybrid routes and with --deep, --ranks, --explain")
+                        "and --host_fusion routes, and with --fusion_filtered the hybrid route on the GPU "
+                        "(msr_hybrid_deep_filtered); refused on the other GPU-fused hybrid routes and with --deep, --ranks, "
+                        "--explain")
     s.add_argument("--query_sets", default=None, metavar="FILE",
                    help="filtered search: TSV lines qid<TAB>set; a query without a line is unfiltered")
     s.add_argument("--ranks", action="store_true",

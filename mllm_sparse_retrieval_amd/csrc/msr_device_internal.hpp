@@ -369,6 +369,8 @@ int launch_score_dump(hipStream_t st, uint32_t tile_docs, uint32_t n_tiles, cons
 int launch_score_filtered(hipStream_t st, uint32_t tile_docs, uint32_t t_begin, uint32_t t_end, const ScoreArgs& a0,
                           const FilterArgs& f);
 int launch_select_filtered(hipStream_t st, uint32_t tile_docs, const SelectArgs& a, const FilterArgs& f);
+int launch_score_dump_filtered(hipStream_t st, uint32_t tile_docs, uint32_t n_tiles, const ScoreArgs& a0, const FilterArgs& f);
+int launch_mask_key_rows(hipStream_t st, uint32_t* D, uint64_t ld, uint32_t rows, uint32_t q0, const FilterArgs& f);
 
 }  // namespace msr
 

@@ -2636,15 +2636,28 @@ int msr_hybrid_sweep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const i
 // ones) and never below one block, so an index whose one block of rows is larger is still served, one block per pass.
 constexpr uint64_t kHybridDeepPassBytes = 256ull << 20;
 
-int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
-                    const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas, int n_alphas,
-                    uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
-                    int32_t* out_n, uint32_t* out_members, uint8_t* out_src, uint32_t* out_sparse_ord,
-                    uint32_t* out_sparse_u32, int32_t* out_sparse_n, uint32_t* out_dense_ord, float* out_dense,
-                    int32_t* out_dense_n, float* out_range, float ms[6]) {
-    const char* const who = "msr_hybrid_deep";
+// The doc sets of an msr_hybrid_deep_filtered call as the caller passed them.
+struct HybridDeepFilter {
+    const uint32_t* set_bits;
+    int n_sets;
+    const int32_t* q_set;
+};
+
+}  // extern "C"
+
+// msr_hybrid_deep (flt = null, 6 time slots) and msr_hybrid_deep_filtered (7 slots). Under a filter a pass with at least
+// one filtered query launches score_dump_filtered in the place of the dump and mask_key_rows after the GEMM; every other
+// launch, and every launch of a pass without a filtered query, is msr_hybrid_deep's.
+static int hybrid_deep_impl(const char* const who, msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term,
+                            const int32_t* q_w, const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas,
+                            int n_alphas, uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord,
+                            const HybridDeepFilter* flt, uint32_t* out_ord, float* out_score, int32_t* out_n,
+                            uint32_t* out_members, uint8_t* out_src, uint32_t* out_sparse_ord, uint32_t* out_sparse_u32,
+                            int32_t* out_sparse_n, uint32_t* out_dense_ord, float* out_dense, int32_t* out_dense_n,
+                            float* out_range, float* ms) {
+    const int n_ms = flt ? 7 : 6;
     if (ms)
-        for (int i = 0; i < 6; ++i) ms[i] = 0.f;
+        for (int i = 0; i < n_ms; ++i) ms[i] = 0.f;
     // ---- checks, all before any device work: shapes and handles, then ranges, then the device
     if (!ix || !dx || !q_ptr || !row2ord || !alphas || !out_ord || !out_score || !out_n || !out_members || nq < 0 || (nq && !q)) {
         set_error("%s: bad argument", who);
@@ -2663,6 +2676,8 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
             set_error("%s: alphas[%d] is not finite", who, i);
             return MSR_E_INVAL;
         }
+    if (flt)
+        if (int rc0 = filter_check_shapes(who, flt->set_bits, flt->n_sets, flt->q_set)) return rc0;
     if (depth < 1 || depth > MSR_DEEP_KMAX) {
         set_error("%s: depth must be in [1, MSR_DEEP_KMAX = %d] (got %d)", who, MSR_DEEP_KMAX, depth);
         return MSR_E_RANGE;
@@ -2676,6 +2691,8 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
         set_error("%s: n_alphas must be in [1, %d] (got %d)", who, MSR_SWEEP_MAX_ALPHAS, n_alphas);
         return MSR_E_RANGE;
     }
+    if (flt)
+        if (int rc0 = filter_check_ranges(who, flt->n_sets, flt->q_set, nq)) return rc0;
     if (h->n_docs > 0x7FFFFFFFull) {
         set_error("%s: %llu docs exceed the 2^31 - 1 columns of a score row", who, (unsigned long long)h->n_docs);
         return MSR_E_RANGE;
@@ -2700,6 +2717,28 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
     const uint64_t ld_s = (uint64_t)h->n_tiles * h->tile_docs;  // the dump's row: tile t starts at column t * tile_docs
     const uint64_t n_cover = std::min<uint64_t>(dx->n_pad, ((uint64_t)n + 255) / 256 * 256);
     const uint64_t ld_d = std::max<uint64_t>(n_cover, 4);
+    // ---- the doc sets, with the call's own upload (bitmap | any | q_set, one block): ONE image over doc ordinals serves
+    // both rows, the GEMM runs on the ordinal-ordered rows
+    FilterImage fi;
+    FilterArgs fa = {};
+    bool any_filtered = false;
+    for (int i = 0; flt && flt->n_sets > 0 && i < nq && !any_filtered; ++i) any_filtered = !flt->q_set || flt->q_set[i] >= 0;
+    if (any_filtered) {
+        if (ld_s > 0xFFFFFFFFull || ld_d > ld_s) {  // (a bitmap row covers every vec of both rows: mask_key_rows reads up to ld_d)
+            set_error("%s: key rows of %llu columns against doc-set rows of %llu bits", who, (unsigned long long)ld_d,
+                      (unsigned long long)ld_s);
+            return MSR_E_RANGE;
+        }
+        fi.build(flt->set_bits, flt->n_sets, flt->q_set, nq, h->n_docs, h->tile_docs, h->n_tiles);
+        const size_t o_bits = cs.put(fi.bits), o_any = cs.put(fi.any), o_qs = cs.put(fi.q_set);
+        const uint32_t* d_in = cs.upload("doc sets", &rc);
+        if (!d_in) return rc;
+        fa.bits = d_in + o_bits;
+        fa.any = reinterpret_cast<const uint8_t*>(d_in + o_any);
+        fa.q_set = reinterpret_cast<const int32_t*>(d_in + o_qs);
+        fa.stride = fi.stride;
+        fa.n_tiles = h->n_tiles;
+    }
     const uint32_t gb = hybrid_gemm_block(dx);
     const uint32_t nq_pad = (uint32_t)(((uint64_t)nq + gb - 1) / gb * gb);
     const uint64_t rb = std::max<uint64_t>(1, kHybridDeepPassBytes / (std::max(ld_s, ld_d) * 4 * gb));
@@ -2740,13 +2779,17 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
         return MSR_E_HIP;
     // laps of a pass: 0 | scoring | 1 | upload + GEMM | 2 | depth selections | 3, and per alpha 4 + 3a | fuse_rows | 5 + 3a |
     // selection | 6 + 3a (the copies to the host lie between the alphas' laps)
-    if ((rc = cs.laps(4 + 3 * n_alphas, ms != nullptr))) return rc;
-    double t[5] = {0, 0, 0, 0, 0};
+    // (a filtered pass: ... GEMM | 2 | mask_key_rows | lap_mask | depth selections | 3)
+    const int lap_mask = 4 + 3 * n_alphas;
+    if ((rc = cs.laps(lap_mask + (any_filtered ? 1 : 0), ms != nullptr))) return rc;
+    double t[5] = {0, 0, 0, 0, 0}, t_mask = 0;
     uint32_t passes = 0;
     const size_t nqk = (size_t)nq * k;
     for (uint32_t q0 = 0; q0 < (uint32_t)nq; q0 += qt, ++passes) {
         const uint32_t qn = std::min<uint32_t>(qt, (uint32_t)nq - q0);
         const uint32_t qn_pad = (qn + gb - 1) / gb * gb;
+        bool pass_filtered = false;
+        for (uint32_t i = 0; any_filtered && i < qn && !pass_filtered; ++i) pass_filtered = (int32_t)fi.q_set[q0 + i] >= 0;
         // 1. the sparse dump, exactly as msr_search_deep launches it: row q - q0, column = doc ordinal
         ScoreArgs sa;
         fill_score_args(sa, b, 1);
@@ -2757,7 +2800,9 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
         sa.tpr = h->n_tiles;
         sa.dump_add = 0;
         if ((rc = cs.mark(0))) return rc;
-        if ((rc = launch_score_dump(d->stream, h->tile_docs, h->n_tiles, sa))) return rc;
+        if ((rc = pass_filtered ? launch_score_dump_filtered(d->stream, h->tile_docs, h->n_tiles, sa, fa)
+                                : launch_score_dump(d->stream, h->tile_docs, h->n_tiles, sa)))
+            return rc;
         if ((rc = cs.mark(1))) return rc;
         // 2. the hybrid GEMM on the ordinal-ordered rows, writing keys
         if (!upload_query_rows(dx, d_Q, (const uint8_t*)q + (size_t)q0 * h_row, qn, qn_pad, d->stream)) {
@@ -2766,6 +2811,10 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
         }
         if ((rc = launch_hybrid_gemm(dx, d_Q, d_D, qn, qn_pad, n_cover, ld_d, d->stream, false))) return rc;
         if ((rc = cs.mark(2))) return rc;
+        if (pass_filtered) {  // the dense keys of the non-members become 0 = "no member"
+            if ((rc = launch_mask_key_rows(d->stream, d_D, ld_d, qn, q0, fa))) return rc;
+            if ((rc = cs.mark(lap_mask))) return rc;
+        }
         // 3. both depth lists
         DeepArgs da;
         da.n = n;
@@ -2830,8 +2879,13 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
             return MSR_E_HIP;
         for (int i = 0; i < 3; ++i) {
             float x = 0;
-            if ((rc = cs.elapsed(i, i + 1, &x))) return rc;
+            if ((rc = cs.elapsed(i == 2 && pass_filtered ? lap_mask : i, i + 1, &x))) return rc;
             t[i] += x;
+        }
+        if (pass_filtered) {
+            float x = 0;
+            if ((rc = cs.elapsed(2, lap_mask, &x))) return rc;
+            t_mask += x;
         }
         for (int ai = 0; ai < n_alphas; ++ai) {
             float x = 0, y = 0;
@@ -2854,9 +2908,36 @@ int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const in
     if (ms) {
         for (int i = 0; i < 5; ++i) ms[i] = (float)t[i];
         ms[5] = (float)passes;
+        if (flt) ms[6] = (float)t_mask;
     }
     cs.ok = true;
     return MSR_OK;
+}
+
+extern "C" {
+
+int msr_hybrid_deep(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                    const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas, int n_alphas,
+                    uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord, uint32_t* out_ord, float* out_score,
+                    int32_t* out_n, uint32_t* out_members, uint8_t* out_src, uint32_t* out_sparse_ord,
+                    uint32_t* out_sparse_u32, int32_t* out_sparse_n, uint32_t* out_dense_ord, float* out_dense,
+                    int32_t* out_dense_n, float* out_range, float ms[6]) {
+    return hybrid_deep_impl("msr_hybrid_deep", ix, dx, q_ptr, q_term, q_w, q, q_is_f32, nq, depth, k, alphas, n_alphas, flags,
+                            row2ord, self_ord, nullptr, out_ord, out_score, out_n, out_members, out_src, out_sparse_ord,
+                            out_sparse_u32, out_sparse_n, out_dense_ord, out_dense, out_dense_n, out_range, ms);
+}
+
+int msr_hybrid_deep_filtered(msr_index* ix, msr_dense* dx, const int64_t* q_ptr, const int32_t* q_term, const int32_t* q_w,
+                             const void* q, int q_is_f32, int nq, int depth, int k, const float* alphas, int n_alphas,
+                             uint32_t flags, const uint32_t* row2ord, const int32_t* self_ord, const uint32_t* set_bits,
+                             int n_sets, const int32_t* q_set, uint32_t* out_ord, float* out_score, int32_t* out_n,
+                             uint32_t* out_members, uint8_t* out_src, uint32_t* out_sparse_ord, uint32_t* out_sparse_u32,
+                             int32_t* out_sparse_n, uint32_t* out_dense_ord, float* out_dense, int32_t* out_dense_n,
+                             float* out_range, float ms[7]) {
+    const HybridDeepFilter flt = {set_bits, n_sets, q_set};
+    return hybrid_deep_impl("msr_hybrid_deep_filtered", ix, dx, q_ptr, q_term, q_w, q, q_is_f32, nq, depth, k, alphas, n_alphas,
+                            flags, row2ord, self_ord, &flt, out_ord, out_score, out_n, out_members, out_src, out_sparse_ord,
+                            out_sparse_u32, out_sparse_n, out_dense_ord, out_dense, out_dense_n, out_range, ms);
 }
 
 }  // extern "C"

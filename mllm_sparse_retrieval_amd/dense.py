@@ -442,6 +442,29 @@ def hybrid_deep(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k,
        sparse), the sparse depth list (sparse_ords, sparse_u32 [nq, depth], sparse_n [nq]), the dense one (dense_ords,
        dense float32 scores, dense_n), score_range [nq, 4]; None for each otherwise. ms: kernel ms per stage (sparse,
        dense_gemm, depth_select, fuse_rows, fused_select) and passes."""
+    return _hybrid_deep_call(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k, alphas, row2ord, None, self_ord,
+                             drop_df_eq_n, with_lists)
+
+
+def hybrid_deep_filtered(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k, alphas, row2ord, sets, q_set=None,
+                         self_ord=None, drop_df_eq_n=True, with_lists=True):
+    """hybrid_deep among the docs of each query's set (msr_hybrid_deep_filtered): both depth lists, the extremes and the
+    fused union are those of an index that holds only the set's docs. `sets`: bool [n_sets, n_docs] or packed uint32
+    [n_sets, (n_docs + 31) // 32] over doc ORDINALS (one bitmap serves both sides); q_set[i] in [-1, n_sets), -1 =
+    unfiltered (None: no set, or one set for every query). A full set, -1 and no set give hybrid_deep bit for bit; an
+    empty set gives n = members = 0 and empty depth lists. Same arguments otherwise and the same HybridDeep as
+    hybrid_deep; ms gains `mask` (mask_key_rows, summed over the passes; 0 when no query is filtered)."""
+    from .filters import as_packed_sets, as_q_set
+
+    bits = as_packed_sets(sets, sparse_index.n_docs)
+    qs = as_q_set(q_set, len(np.asarray(q_ptr)) - 1, bits.shape[0])
+    return _hybrid_deep_call(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k, alphas, row2ord, (bits, qs),
+                             self_ord, drop_df_eq_n, with_lists)
+
+
+def _hybrid_deep_call(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k, alphas, row2ord, flt, self_ord,
+                      drop_df_eq_n, with_lists):
+    """One msr_hybrid_deep call, or with flt = (packed sets, q_set) one msr_hybrid_deep_filtered call."""
     from . import _cabi
     from ._cabi import MSR_DEEP_KMAX, MSR_F_DROP_DF_EQ_N, MSR_SWEEP_MAX_ALPHAS
 
@@ -482,11 +505,17 @@ def hybrid_deep(sparse_index, dense_index, q_ptr, q_term, q_w, q_reps, depth, k,
         s_ord, s_u32, s_n = np.empty((nq, depth), np.uint32), np.empty((nq, depth), np.uint32), np.zeros(nq, np.int32)
         d_ord, d_sc, d_n = np.empty((nq, depth), np.uint32), np.empty((nq, depth), np.float32), np.zeros(nq, np.int32)
         rng = np.zeros((nq, 4), dtype=np.float32)
-    ms = (C.c_float * 6)()
-    check(lib().msr_hybrid_deep(sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w), ptr(q), 1 if f32 else 0,
-                                nq, depth, k, ptr(al), int(al.size), MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord),
-                                ptr(so), ptr(ords), ptr(sc), ptr(n), ptr(members), ptr(src), ptr(s_ord), ptr(s_u32), ptr(s_n),
-                                ptr(d_ord), ptr(d_sc), ptr(d_n), ptr(rng), ms))
-    return HybridDeep(ords, sc, n, members, src, s_ord, s_u32, s_n, d_ord, d_sc, d_n, rng,
-                      dict(sparse=ms[0], dense_gemm=ms[1], depth_select=ms[2], fuse_rows=ms[3], fused_select=ms[4],
-                           passes=int(ms[5])))
+    ms = (C.c_float * 7)()
+    head = (sparse_index._h, dense_index._h, ptr(q_ptr), ptr(q_term), ptr(q_w), ptr(q), 1 if f32 else 0, nq, depth, k, ptr(al),
+            int(al.size), MSR_F_DROP_DF_EQ_N if drop_df_eq_n else 0, ptr(row2ord), ptr(so))
+    outs = (ptr(ords), ptr(sc), ptr(n), ptr(members), ptr(src), ptr(s_ord), ptr(s_u32), ptr(s_n), ptr(d_ord), ptr(d_sc),
+            ptr(d_n), ptr(rng), ms)
+    if flt is None:
+        check(lib().msr_hybrid_deep(*head, *outs))
+    else:
+        bits, qs = flt
+        check(lib().msr_hybrid_deep_filtered(*head, ptr(bits) if bits.shape[0] else None, int(bits.shape[0]), ptr(qs), *outs))
+    times = dict(sparse=ms[0], dense_gemm=ms[1], depth_select=ms[2], fuse_rows=ms[3], fused_select=ms[4], passes=int(ms[5]))
+    if flt is not None:
+        times["mask"] = ms[6]
+    return HybridDeep(ords, sc, n, members, src, s_ord, s_u32, s_n, d_ord, d_sc, d_n, rng, times)

@@ -290,34 +290,47 @@ struct LightTile {
     int rounds;               // rounds of 4*NT accumulators that hold real docs
 };
 
-// `init_barrier()` runs between the accumulator init and the first LDS atomic and must hold the workgroup barrier
-// (score_tiles resets the selection scratch before it, score_tiles_walk seeds the candidate buffer after it).
-template <int TILE_DOCS, int NT, class InitBarrier>
-__device__ __forceinline__ void accumulate_light(const LightQuery& lq, const LightTile& lt, uint8_t* const lds,
-                                                 const uint32_t tid, InitBarrier&& init_barrier) {
-    constexpr int NW = NT / 64;
-    constexpr int UL = 4;  // chunk loads per wave and batch
-    static_assert(TILE_DOCS % (4 * NT) == 0, "tile must be a multiple of 4*NT");
-    uint32_t* const acc = reinterpret_cast<uint32_t*>(lds);
-    const uint32_t lane = tid & 63;
-    const uint32_t lane16 = lane * 16u;
-    const uint32_t wave = rfl(tid >> 6);
-    uint4* const a4 = reinterpret_cast<uint4*>(acc);
-
-    const global_u32 seg_row = lt.seg_row;
-    const uint32_t tile_first = lt.tile_first;
-    const char* const post_base = lt.post_base;
-    const int rounds = lt.rounds;
-    const bool has = lane < lq.cnt;
-    const uint32_t s_t = lq.s_t, s_w = lq.s_w;
-    // chunk data of this wave's first UL chunks: requested inside the init phase, consumed after it
+// A wave's share of one tile's sparse postings, in steps that a kernel may place apart (score_tiles runs them back to
+// back inside the accumulator init; score_tiles_walk runs the first three for tile t+1 around tile t's selection):
+//     lookup   request the lane's segment bounds in the tile's row (no wait)
+//     scan     bounds -> segment table (lane j = term j), DPP scan of the chunk counts, this wave's chunk count
+//     request  resolve chunks u0 .. u0+UL-1 of this wave (chunk c -> wave c % NW) and request their postings
+//     add      LDS adds of the requested chunks
+// Chunk byte lengths and query weights of the requested slots are wave-uniform (SGPRs).
+template <int NW>
+struct LightChunks {
+    static constexpr int UL = 4;  // chunk loads per wave and batch
     uint4 v[UL];
     uint32_t n16[UL], wq[UL];
-    uint32_t s_start = 0, s_len = 0, pref = 0, count_w = 0;
-    auto resolve_and_load = [&](uint32_t u0) {  // chunks u0 .. u0+UL-1 of this wave (chunk index c = wave + u * NW)
+    uint32_t s0, s1;              // lane j < cnt: bounds of term j's segment (vecs), as loaded
+    uint32_t s_start, s_len, pref;
+    uint32_t count_w;             // chunks of this wave in the tile
+
+    __device__ __forceinline__ void lookup(const LightQuery& lq, const global_u32 seg_row, const uint32_t lane) {
+        s0 = s1 = 0;
+        if (lane < lq.cnt) {
+            // (a 32-bit byte offset from the uniform row base — a row is shorter than 4 GiB, checked when the index is
+            // attached — so the lookups need one address register, not two 64-bit pairs)
+            const global_u32 seg = (global_u32)((const __attribute__((address_space(1))) char*)seg_row + (lq.s_t << 2));
+            s0 = seg[0];
+            s1 = seg[1];
+        }
+    }
+    __device__ __forceinline__ void scan(const uint32_t tile_first, const uint32_t wave) {
+        s_start = s0 - tile_first;  // vec index inside the tile
+        s_len = s1 - s0;
+        const uint32_t nch = (s_len + (uint32_t)kChunkVecs - 1) / (uint32_t)kChunkVecs;
+        const uint32_t inc = wave_inclusive_scan_u32(nch);
+        pref = inc - nch;
+        const uint32_t total = rdl(inc, 63);
+        count_w = total > wave ? (total - wave + NW - 1) / NW : 0u;
+    }
+    __device__ __forceinline__ void request(const LightQuery& lq, const char* const post_base, const uint32_t u0,
+                                            const uint32_t wave, const uint32_t lane) {
+        const bool has = lane < lq.cnt;
 #pragma unroll
         for (int u = 0; u < UL; ++u) {
-            n16[u] = 0;  // (an idle slot: v[u] and wq[u] are not read)
+            n16[u] = wq[u] = 0;  // (an idle slot: v[u] and wq[u] are not read)
             if (u0 + (uint32_t)u < count_w) {  // wave-uniform: most waves of a light query hold one or two chunks
                 const uint32_t c = wave + (u0 + (uint32_t)u) * NW;
                 // pref is non-decreasing over the lanes: the lanes with pref <= c are a prefix, its last lane owns chunk c
@@ -325,99 +338,113 @@ __device__ __forceinline__ void accumulate_light(const LightQuery& lq, const Lig
                 const uint32_t voff = (c - rdl(pref, lo)) << 6;  // vecs into the segment
                 const uint32_t b16 = (rdl(s_start, lo) + voff) << 4;
                 n16[u] = min(64u, rdl(s_len, lo) - voff) << 4;
-                wq[u] = rdl(s_w, lo);
+                wq[u] = rdl(lq.s_w, lo);
                 // (the chunk's END in the resource's size word: lanes past it read zeros without a request)
-                v[u] = buf_load16(make_rsrc(post_base, b16 + n16[u]), lane16, b16);
+                v[u] = buf_load16(make_rsrc(post_base, b16 + n16[u]), lane * 16u, b16);
             }
         }
-    };
-    auto add_loaded = [&]() {
+    }
+    __device__ __forceinline__ void add(uint32_t* const acc, const uint32_t lane) const {
+        const uint32_t lane16 = lane * 16u;
 #pragma unroll
         for (int u = 0; u < UL; ++u)
             if (n16[u] != 0 && lane16 < n16[u]) {  // (n16 is wave-uniform: an idle slot costs one scalar compare)
                 const uint32_t p[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+                // (the weight stays in its SGPR up to here: a kernel that holds the slots across other work would
+                // otherwise carry a vector copy of it all the way)
+                uint32_t w = rfl(wq[u]);
+                asm volatile("" : "+s"(w));
 #pragma unroll
-                for (int e = 0; e < 4; ++e) atomicAdd(&acc[p[e] & 0xFFFFu], __umul24(p[e] >> 16, wq[u]));
+                for (int e = 0; e < 4; ++e) atomicAdd(&acc[p[e] & 0xFFFFu], __umul24(p[e] >> 16, w));
             }
-    };
-    auto lookup_and_scan = [&]() {  // segment table and chunk scan: per wave, in registers
-        if (has) {
-            // (a 32-bit byte offset from the uniform row base — a row is shorter than 4 GiB, checked when the index is
-            // attached — so the lookups need one address register, not two 64-bit pairs)
-            const global_u32 seg = (global_u32)((const __attribute__((address_space(1))) char*)seg_row + (s_t << 2));
-            const uint32_t s0 = seg[0], s1 = seg[1];
-            s_start = s0 - tile_first;
-            s_len = s1 - s0;
+    }
+    // more than UL chunks for this wave (rare on this path): the segments are looked up again, L2-hot, instead of the
+    // table living in three registers from the first request on, where the kernels that walk several tiles have none
+    // to spare
+    __device__ __forceinline__ void add_leftover(const LightQuery& lq, const LightTile& lt, uint32_t* const acc,
+                                                 const uint32_t wave, const uint32_t lane) {
+        if (count_w > UL) {
+            lookup(lq, lt.seg_row, lane);
+            scan(lt.tile_first, wave);
+            for (uint32_t u0 = UL; u0 < count_w; u0 += UL) {
+                request(lq, lt.post_base, u0, wave, lane);
+                add(acc, lane);
+            }
         }
-        const uint32_t nch = (s_len + (uint32_t)kChunkVecs - 1) / (uint32_t)kChunkVecs;
-        const uint32_t inc = wave_inclusive_scan_u32(nch);
-        pref = inc - nch;
-        const uint32_t total = rdl(inc, 63);
-        count_w = total > wave ? (total - wave + NW - 1) / NW : 0u;
-    };
-    auto prefetch = [&]() {
-        lookup_and_scan();
-        resolve_and_load(0);
-    };
+    }
+};
 
-    // ---- accumulator init (dense-head rows scored by the accumulator's owner, or zero): as in accumulate_tile, with
-    // the sparse prefetch issued right after the first rows have been requested
-    {
-        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-        constexpr int RG = 4;
-        const uint32_t qv = lq.qv;
-        const uint32_t pmask = lq.pmask;
-        const __amdgpu_buffer_rsrc_t rs_dense = make_rsrc(lt.dense, lt.dense_bytes);
-        for (int r0 = 0; r0 < rounds; r0 += RG) {
-            uint4 sacc[RG];
+// Accumulator init: zero, or — when the query holds dense-head terms — their whole contribution (dense-head rows scored
+// by the accumulator's owner, as in accumulate_tile). `after_first_rows()` runs once, right after the first rows have
+// been requested (at the end when there are none): where score_tiles issues its sparse prefetch.
+template <int TILE_DOCS, int NT, class AfterFirstRows>
+__device__ __forceinline__ void light_init(const LightQuery& lq, const LightTile& lt, uint4* const a4,
+                                           const uint32_t tid, AfterFirstRows&& after_first_rows) {
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    constexpr int RG = 4;
+    const int rounds = lt.rounds;
+    const uint32_t qv = lq.qv;
+    const uint32_t pmask = lq.pmask;
+    const __amdgpu_buffer_rsrc_t rs_dense = make_rsrc(lt.dense, lt.dense_bytes);
+    for (int r0 = 0; r0 < rounds; r0 += RG) {
+        uint4 sacc[RG];
 #pragma unroll
-            for (int i = 0; i < RG; ++i) sacc[i] = make_uint4(0, 0, 0, 0);
-            if (pmask) {
-                uint32_t voff[RG];
+        for (int i = 0; i < RG; ++i) sacc[i] = make_uint4(0, 0, 0, 0);
+        if (pmask) {
+            uint32_t voff[RG];
 #pragma unroll
-                for (int i = 0; i < RG; ++i) voff[i] = ((uint32_t)min(r0 + i, rounds - 1) * NT + tid) * 16u;
-                auto load_rows = [&](uint4 (&x)[RG], uint32_t p) {
+            for (int i = 0; i < RG; ++i) voff[i] = ((uint32_t)min(r0 + i, rounds - 1) * NT + tid) * 16u;
+            auto load_rows = [&](uint4 (&x)[RG], uint32_t p) {
 #pragma unroll
-                    for (int i = 0; i < RG; ++i) x[i] = buf_load16(rs_dense, voff[i], p * (uint32_t)(TILE_DOCS * 4));
-                };
-                auto add_rows = [&](const uint4 (&x)[RG], uint32_t qp) {
-                    const us2 qq = __builtin_bit_cast(us2, qp);
+                for (int i = 0; i < RG; ++i) x[i] = buf_load16(rs_dense, voff[i], p * (uint32_t)(TILE_DOCS * 4));
+            };
+            auto add_rows = [&](const uint4 (&x)[RG], uint32_t qp) {
+                const us2 qq = __builtin_bit_cast(us2, qp);
 #pragma unroll
-                    for (int i = 0; i < RG; ++i) {
-                        sacc[i].x = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].x), qq, sacc[i].x, false);
-                        sacc[i].y = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].y), qq, sacc[i].y, false);
-                        sacc[i].z = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].z), qq, sacc[i].z, false);
-                        sacc[i].w = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].w), qq, sacc[i].w, false);
-                    }
-                };
-                uint32_t m = pmask;
-                uint4 xa[RG];
-                for (;;) {  // one pair at a time (light queries hold one or two): the register banks go to the chunks
-                    const uint32_t pa = (uint32_t)__builtin_ctz(m);
-                    m &= m - 1;
-                    load_rows(xa, pa);
-                    if (r0 == 0 && pa == (uint32_t)__builtin_ctz(pmask)) prefetch();
-                    add_rows(xa, rdl(qv, pa));
-                    if (!m) break;
+                for (int i = 0; i < RG; ++i) {
+                    sacc[i].x = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].x), qq, sacc[i].x, false);
+                    sacc[i].y = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].y), qq, sacc[i].y, false);
+                    sacc[i].z = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].z), qq, sacc[i].z, false);
+                    sacc[i].w = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, x[i].w), qq, sacc[i].w, false);
                 }
+            };
+            uint32_t m = pmask;
+            uint4 xa[RG];
+            for (;;) {  // one pair at a time (light queries hold one or two): the register banks go to the chunks
+                const uint32_t pa = (uint32_t)__builtin_ctz(m);
+                m &= m - 1;
+                load_rows(xa, pa);
+                if (r0 == 0 && pa == (uint32_t)__builtin_ctz(pmask)) after_first_rows();
+                add_rows(xa, rdl(qv, pa));
+                if (!m) break;
             }
+        }
 #pragma unroll
-            for (int i = 0; i < RG; ++i)
-                if (r0 + i < rounds) a4[(r0 + i) * NT + tid] = sacc[i];
-        }
-        if (!pmask) prefetch();
+        for (int i = 0; i < RG; ++i)
+            if (r0 + i < rounds) a4[(r0 + i) * NT + tid] = sacc[i];
     }
+    if (!pmask) after_first_rows();
+}
+
+// One tile, start to end: every wave has its first UL chunk loads IN FLIGHT before the accumulators are initialised.
+// `init_barrier()` runs between the accumulator init and the first LDS atomic and must hold the workgroup barrier
+// (score_tiles resets the selection scratch before it).
+template <int TILE_DOCS, int NT, class InitBarrier>
+__device__ __forceinline__ void accumulate_light(const LightQuery& lq, const LightTile& lt, uint8_t* const lds,
+                                                 const uint32_t tid, InitBarrier&& init_barrier) {
+    static_assert(TILE_DOCS % (4 * NT) == 0, "tile must be a multiple of 4*NT");
+    uint32_t* const acc = reinterpret_cast<uint32_t*>(lds);
+    const uint32_t lane = tid & 63;
+    const uint32_t wave = rfl(tid >> 6);
+    LightChunks<NT / 64> ch;
+    light_init<TILE_DOCS, NT>(lq, lt, reinterpret_cast<uint4*>(acc), tid, [&] {
+        ch.lookup(lq, lt.seg_row, lane);
+        ch.scan(lt.tile_first, wave);
+        ch.request(lq, lt.post_base, 0, wave, lane);
+    });
     init_barrier();  // every accumulator is initialised
-    add_loaded();
-    if (count_w > UL) {  // rare on this path: more than UL chunks for one wave
-        // (the segment table is looked up again, L2-hot, instead of living in three registers through the init phase,
-        // where the kernels that walk several tiles have none to spare)
-        lookup_and_scan();
-        for (uint32_t u0 = UL; u0 < count_w; u0 += UL) {
-            resolve_and_load(u0);
-            add_loaded();
-        }
-    }
+    ch.add(acc, lane);
+    ch.add_leftover(lq, lt, acc, wave, lane);
     __syncthreads();  // accumulation complete
 }
 

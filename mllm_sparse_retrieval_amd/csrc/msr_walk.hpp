@@ -7,8 +7,8 @@
 // the lane constants — repeated per (tile, query) workgroup and per wave — and then hand k keys per tile through HBM to
 // two merge launches. Here the query side (LightQuery) is loaded once per workgroup, the tile side of every step is one
 // scalar load from the handle's per-tile table (WalkTile), and the running top-k `best` stays in LDS:
-//     tile 0      accumulate_light, tile_select -> best
-//     tile t > 0  accumulate_light; theta = best[k-1] is a lower bound on the final k-th key, so the tile only has to
+//     tile 0      accumulate (light_init + LightChunks, msr_accumulate.hpp), tile_select -> best
+//     tile t > 0  accumulate; theta = best[k-1] is a lower bound on the final k-th key, so the tile only has to
 //                 report keys at or above it: the candidate buffer is seeded with best's k keys, theta_select appends
 //                 the tile's survivors and ranks the lot back into best. While best is not full (theta = 0), or when
 //                 more keys survive than the buffer holds (mass ties), the tile runs the full tile_select into `side`
@@ -69,41 +69,77 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void score_tiles_walk(const WalkArgs
     uint32_t tid = threadIdx.x;
     LightQuery lq = load_light_query(a.s, q, tid & 63);  // once per workgroup: the same for every tile
 
+    // Software pipeline over the tiles: nothing of a tile's (segment lookup -> scan -> first UL chunk loads per wave)
+    // chain depends on the tile before it, so tile t+1's chain runs while tile t is finished and selected, and its
+    // postings are in registers when tile t+1's accumulators are initialised. Tile 0 is primed here.
+    LightChunks<NT / 64> ch;
+    // (of a tile's table row only the dense-head rows and the doc range are carried into its own iteration: what the
+    // lookup and the requests need is used where the row is loaded)
+    const char* dense;
+    uint32_t doc0_rounds;
+    {
+        const WalkTile wt = load_uniform(a.tiles);  // one scalar load per tile: no address arithmetic per wave and tile
+        dense = wt.dense;
+        doc0_rounds = wt.doc0_rounds;
+        ch.lookup(lq, (global_u32)wt.seg_row, tid & 63);
+        ch.scan(wt.tile_first, rfl(tid >> 6));
+        ch.request(lq, wt.post_base, 0, rfl(tid >> 6), tid & 63);
+    }
+
     for (uint32_t tl = 0; tl < a.n_tiles; ++tl) {
         // a per-tile copy of the thread id: what the tile's phases derive from it (accumulator addresses, doc keys) is
         // recomputed where it is used instead of being hoisted out of the loop into registers the kernel does not have
         asm volatile("" : "+v"(tid), "+v"(lq.s_t), "+v"(lq.s_w), "+v"(lq.qv));
-        const WalkTile wt = load_uniform(a.tiles + tl);  // one scalar load: no address arithmetic per wave and tile
         LightTile lt;
-        lt.seg_row = (global_u32)wt.seg_row;
-        lt.tile_first = wt.tile_first;
-        lt.post_base = wt.post_base;
-        lt.dense = wt.dense;
+        lt.dense = dense;
         lt.dense_bytes = a.s.n_pairs * (uint32_t)(TILE_DOCS * 4);
-        lt.rounds = min((int)(wt.doc0_rounds & kWalkRoundsMask), TILE_DOCS / (4 * NT));
-        const uint64_t doc0 = wt.doc0_rounds & ~kWalkRoundsMask;
+        lt.rounds = min((int)(doc0_rounds & kWalkRoundsMask), TILE_DOCS / (4 * NT));
+        const uint64_t doc0 = doc0_rounds & ~kWalkRoundsMask;
+        const bool more = tl + 1 < a.n_tiles;  // the last tile requests nothing
+        uint32_t* const acc = reinterpret_cast<uint32_t*>(lds);
+        const uint32_t lane = tid & 63, wave = rfl(tid >> 6);
 
+        light_init<TILE_DOCS, NT>(lq, lt, reinterpret_cast<uint4*>(lds), tid, [] {});
+        // every wave has left the previous tile's selection: its ranking of `best` is complete and visible, and
+        // nobody reads the candidate buffer or the scratch of that tile any more
+        __syncthreads();
         uint64_t theta = 0;
-        accumulate_light<TILE_DOCS, NT>(lq, lt, lds, tid, [&] {
-            // every wave has left the previous tile's selection: its ranking of `best` is complete and visible, and
-            // nobody reads the candidate buffer or the scratch of that tile any more
-            __syncthreads();
-            if (tl) {
-                const uint64_t th = best[k - 1];  // 0: fewer than k hits so far
-                theta = ((uint64_t)rfl((uint32_t)(th >> 32)) << 32) | rfl((uint32_t)th);
-            }
-            if (tid < 64) {
-                ss.cnt[tid] = 0;
-                if (theta && tid < k) cand[tid] = best[tid];
-            }
-            if (tid == 0) {
-                uint32_t one = 1;  // (made here, behind an opaque copy: not a constant held in a register across the tiles)
-                asm volatile("" : "+v"(one));
-                ss.n_cand = theta ? k : 0u;
-                ss.tau0 = one;
-                ss.smax = one - 1;
-            }
-        });
+        if (tl) {
+            const uint64_t th = best[k - 1];  // 0: fewer than k hits so far
+            theta = ((uint64_t)rfl((uint32_t)(th >> 32)) << 32) | rfl((uint32_t)th);
+        }
+        if (tid < 64) {
+            ss.cnt[tid] = 0;
+            if (theta && tid < k) cand[tid] = best[tid];
+        }
+        if (tid == 0) {
+            uint32_t one = 1;  // (made here, behind an opaque copy: not a constant held in a register across the tiles)
+            asm volatile("" : "+v"(one));
+            ss.n_cand = theta ? k : 0u;
+            ss.tau0 = one;
+            ss.smax = one - 1;
+        }
+        ch.add(acc, lane);  // the chunks requested before the previous tile's selection (before the loop: tile 0)
+        if (ch.count_w > ch.UL) {  // rare
+            const WalkTile wt = load_uniform(a.tiles + tl);
+            lt.seg_row = (global_u32)wt.seg_row;
+            lt.tile_first = wt.tile_first;
+            lt.post_base = wt.post_base;
+            ch.add_leftover(lq, lt, acc, wave, lane);
+        }
+        // the next tile's segment bounds: requested once this wave's LDS adds are out, so that the wait at the barrier
+        // covers the round trip
+        // (the row is loaded unconditionally — the last tile re-reads its own — so that it stays in scalar registers)
+        const WalkTile nx = load_uniform(a.tiles + min(tl + 1, a.n_tiles - 1));
+        if (more) ch.lookup(lq, (global_u32)nx.seg_row, lane);
+        __syncthreads();  // accumulation complete
+        // ... and its first chunks: the selection's passes and the ranking cover the postings' latency
+        if (more) {
+            ch.scan(nx.tile_first, wave);
+            ch.request(lq, nx.post_base, 0, wave, lane);
+        }
+        dense = nx.dense;
+        doc0_rounds = nx.doc0_rounds;
 
         if (theta && theta_select<TILE_DOCS, NT, CAND>(a4, cand, ss, lt.rounds, doc0, (int)k, best, theta, tid)) continue;
         tile_select<TILE_DOCS, NT, CAND>(a4, cand, tmax, wmax, ss, lt.rounds, doc0, (int)k, tl ? side : best, tid);
